@@ -4,11 +4,16 @@ meshed on the 512^3 uint64 ~50k-label synthetic segmentation chunk
 (configs[2] — the configuration the metric is quoted on), one process per
 GPU, weak scaling (each rank meshes its own chunk per step).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --full ...
 
-With no mode flags, FOUR benches run back-to-back and all appear in the
-single JSON line's "configs" array (the top-level value/ms_per_step stay
-the headline configs[2] device rate):
+A plain run does only what the headline figure needs: it loads the chunk,
+warms up, times K steps of the mc bench below and prints the JSON line.
+--dump-outputs DIR then also writes the meshes of the headline bench as
+DIR/<name>.npy (see dump_outputs). With --full, FOUR benches run
+back-to-back and all appear in the single JSON line's "configs" array (the
+top-level value/ms_per_step stay the headline configs[2] device rate),
+followed by the CPU baseline:
   - mc             BASELINE configs[2]: 512^3 u64 device-resident MC-only
   - simplify       BASELINE configs[4] ("config 5"): same chunk with
                    simplification_factor=100, max_error=40
@@ -18,6 +23,10 @@ the headline configs[2] device rate):
   - chunks256_prod the same fan-out with the reference's production
                    default simplification_factor=100
 --mode/--simplify restrict the run to one bench (targeted profiling).
+
+The 512^3 input chunk is deterministic (seeded) and cached in-tree under
+.bench_cache/; __graft_entry__.build() stages it so a run does not pay the
+~30 s generation.
 
 For N>1 the driver launches this under torch.distributed.run with one rank
 per GPU; ranks synchronize with a barrier + torch.cuda.synchronize around
@@ -29,7 +38,7 @@ For the device-resident benches inputs are in HBM when the timed region
 starts (staged in warmup; MG_FLAG_SKIP_H2D); the chunks256 bench times the
 PCIe-inclusive production path and says so in its config.
 
-cpu_baseline: this repo's CPU oracle (oracle/, kind "port" — zmesh is not
+cpu_baseline (--full only): this repo's CPU oracle (oracle/, kind "port" — zmesh is not
 installable offline) timed on the host's cores over a bounded
 sample of the same workload, igneous's own process-per-chunk parallelism
 model (cli.py:915-933).
@@ -52,6 +61,19 @@ K_SEEDS = 50000
 SEED = 303
 RESOLUTION = (16.0, 16.0, 40.0)
 PEAK_HBM = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md)
+BENCH_CACHE = os.path.join(REPO, ".bench_cache")
+DUMP_SEED = 20240607
+DUMP_LABELS = 256           # labels sampled into the --dump-outputs files
+                            # (~130 KB of mesh each at reduction 0)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def bench_input() -> np.ndarray:
+    """The headline chunk (seeded, identical from run to run), cached
+    in-tree so that build() can stage it ahead of the first run."""
+    from igneous_amd.synth import voronoi_labels
+    return voronoi_labels(SHAPE, K_SEEDS, SEED, dtype=np.uint64,
+                          cache_dir=BENCH_CACHE)
 
 
 _BASE_DATA = None   # fork-shared (copy-on-write) chunk for baseline workers
@@ -157,6 +179,62 @@ def run_chunk512(eng, data, steps, warmup, simplify, barrier_sync, max_rank):
     }
 
 
+def dump_outputs(eng, data, simplify, last_stats, outdir):
+    """Write what the headline chunk512 bench computed as outdir/<name>.npy
+    (float32/float64 only, < 64 MB in all), for output-by-output comparison
+    of two builds.
+
+    The timed step runs under MG_FLAG_DEVICE_ONLY: its caller receives the
+    size counters only, the meshes stay in HBM. `counts` is therefore taken
+    from the LAST TIMED step's stats; the meshes are fetched by one more,
+    untimed, call with the same arguments minus DEVICE_ONLY (the engine is
+    deterministic, tests/test_gpu_parity.py pins that). All labels' sizes
+    are written; vertices and faces of a fixed seeded sample of labels.
+
+      counts       f64 [3]    total_tris, total_verts, n_labels (pre-
+                              simplification), last timed step
+      labels       f64 [L]    every meshed label id, ascending (< 2^53)
+      nverts       f64 [L]    vertices per label
+      nfaces       f64 [L]    triangles per label
+      sample_index f64 [S]    positions in `labels` of the sampled labels
+      sample_verts f32 [*,3]  their vertices (chunk-local nm), concatenated
+      sample_faces f64 [*,3]  their label-local face indices, concatenated
+    """
+    red = 100 if simplify else 0
+    got = eng.mesh_chunk(data, resolution=RESOLUTION, reduction_factor=red,
+                         max_error=40.0, skip_h2d=True)
+    labels = sorted(got.keys())
+    nlab = len(labels)
+    nverts = np.array([got[l][0].shape[0] for l in labels], dtype=np.float64)
+    nfaces = np.array([got[l][1].shape[0] for l in labels], dtype=np.float64)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(nlab, size=min(DUMP_LABELS, nlab),
+                              replace=False)) if nlab else np.zeros(0, int)
+    fixed = 3 * 8 + 3 * 8 * nlab
+    per_label = 12 * nverts[pick] + 24 * nfaces[pick] + 8
+    keep = int(np.searchsorted(np.cumsum(per_label),
+                               DUMP_MAX_BYTES - fixed - 4096, side="right"))
+    pick = pick[:keep]
+    sv = [got[labels[i]][0] for i in pick]
+    sf = [got[labels[i]][1] for i in pick]
+    arrays = {
+        "counts": np.array([last_stats["total_tris"],
+                            last_stats["total_verts"],
+                            last_stats["n_labels"]], dtype=np.float64),
+        "labels": np.array(labels, dtype=np.float64),
+        "nverts": nverts,
+        "nfaces": nfaces,
+        "sample_index": pick.astype(np.float64),
+        "sample_verts": (np.concatenate(sv) if sv else
+                         np.zeros((0, 3))).astype(np.float32),
+        "sample_faces": (np.concatenate(sf) if sf else
+                         np.zeros((0, 3))).astype(np.float64),
+    }
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def run_chunks256(local_rank, ndev, steps, warmup, streams,
                   barrier_sync, max_rank, red=0, name="chunks256"):
     """BASELINE configs[3] shape: independent 256^3 chunks, FULL path
@@ -239,12 +317,23 @@ def main():
                     help="run ONLY the config-5 bench (simplification_"
                          "factor=100, max_error=40)")
     ap.add_argument("--mode", choices=["all", "chunk512", "chunks256"],
-                    default="all",
-                    help="all: mc + simplify + chunks256 benches (default); "
-                         "chunk512: only the single-chunk device bench; "
+                    default=None,
+                    help="all: mc + simplify + chunks256 benches (default "
+                         "with --full); chunk512: only the single-chunk "
+                         "device bench (default without --full); "
                          "chunks256: only the full-path fan-out bench")
     ap.add_argument("--streams", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the non-headline benches (unless --mode/"
+                         "--simplify picks one) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the headline bench's "
+                         "outputs as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.mode is None:
+        args.mode = "all" if args.full else "chunk512"
+    if args.dump_outputs and args.mode == "chunks256" and not args.simplify:
+        ap.error("--dump-outputs needs a chunk512 headline bench")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,7 +368,6 @@ def main():
         return float(t.item())
 
     from igneous_amd.engine import Engine, load_library
-    from igneous_amd.synth import voronoi_labels
 
     # weak scaling: every rank meshes its own copy of the same synthetic
     # chunk (chunks are independent; identical per-rank work). Rank 0
@@ -287,7 +375,7 @@ def main():
     # cache instead of N concurrent generations.
     if dist is not None and rank != 0:
         dist.barrier()
-    data = voronoi_labels(SHAPE, K_SEEDS, SEED, dtype=np.uint64)
+    data = bench_input()
     if dist is not None and rank == 0:
         dist.barrier()
     ndev = max(1, load_library().mg_device_count())
@@ -324,6 +412,10 @@ def main():
                                          args.warmup, args.streams,
                                          barrier_sync, max_rank,
                                          red=100, name="chunks256_prod"))
+        if args.dump_outputs and rank == 0 and len(results) == 1:
+            # headline bench just finished: its ctx still holds the chunk
+            dump_outputs(eng, data, name == "simplify", results[0]["stats"],
+                         args.dump_outputs)
 
     for r in results:
         total_vox = r["step_vox"] * args.steps * world
@@ -365,7 +457,7 @@ def main():
         }
 
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu = cpu_baseline(data, reduction=100 if args.simplify else 0)
 
     line = {

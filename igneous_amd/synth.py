@@ -11,13 +11,16 @@ import numpy as np
 
 def voronoi_labels(shape, K: int, seed: int, dtype=np.uint64,
                    background_frac: float = 0.03,
-                   cache: bool = True) -> np.ndarray:
+                   cache: bool = True,
+                   cache_dir: str | None = None) -> np.ndarray:
     """F-order (sx,sy,sz) label volume. Deterministic; large volumes are
-    cached on local disk (generation of 512^3/K=50k takes ~30 s)."""
+    cached on local disk (generation of 512^3/K=50k takes ~30 s) under
+    $MESHGINE_CACHE, else cache_dir, else /tmp/meshgine_cache."""
     import os
     cache_path = None
     if cache and int(np.prod(shape)) >= 64 ** 3:
-        cdir = os.environ.get("MESHGINE_CACHE", "/tmp/meshgine_cache")
+        cdir = os.environ.get("MESHGINE_CACHE",
+                              cache_dir or "/tmp/meshgine_cache")
         os.makedirs(cdir, exist_ok=True)
         tag = "x".join(str(int(s)) for s in shape)
         cache_path = os.path.join(

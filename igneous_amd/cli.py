@@ -26,6 +26,15 @@ def _vec3(_ctx, _param, value):
     return tuple(parts)
 
 
+def _int_list(_ctx, _param, value):
+    if value is None:
+        return None
+    try:
+        return [int(x) for x in str(value).split(",") if x.strip() != ""]
+    except ValueError:
+        raise click.BadParameter("expected comma separated integers")
+
+
 @click.group()
 def main():
     """igneous_amd — MI355X-native meshing with igneous's API."""
@@ -60,11 +69,15 @@ def mesh():
 @click.option("--fill-missing", is_flag=True, default=False)
 @click.option("--closed-edge/--open-edge", default=True,
               help="close meshes at dataset boundaries")
+@click.option("--labels", default=None, callback=_int_list,
+              help="mesh only this comma separated list of labels")
+@click.option("--exclude-labels", default=None, callback=_int_list,
+              help="do not mesh labels in this comma separated list")
 @click.option("--no-execute", is_flag=True, default=False,
               help="only create tasks + mesh info; do not run them")
 def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
           mesh_dir, compress, spatial_index, sharded, fill_missing,
-          closed_edge, no_execute):
+          closed_edge, labels, exclude_labels, no_execute):
     """(Re)Generate meshes for the segmentation at PATH
     (reference mesh_forge, cli.py:1035-1071)."""
     tasks = create_meshing_tasks(
@@ -78,6 +91,8 @@ def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
         fill_missing=fill_missing,
         compress=(None if compress in ("none", "False", "") else compress),
         closed_dataset_edges=closed_edge,
+        object_ids=labels,
+        exclude_object_ids=(exclude_labels or []),
     )
     click.echo(f"{len(tasks)} MeshTasks over {path}")
     if no_execute:

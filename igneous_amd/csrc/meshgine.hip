@@ -13,6 +13,10 @@
 //
 // Device pipeline (one mg_mesh_chunk call):
 //   H2D labels
+//   [0] (optional) k_dust_*: zero labels below dust_threshold;
+//       (optional, mg_mesh_chunk_mapped) k_map_build + k_label_map:
+//       remap_table / object_ids / exclude_object_ids as one table lookup
+//       per voxel, in place
 //   [1] k_count        wave-per-64-cell-segment triangle counts
 //                      (+ label hash build)                    -> segcnt
 //   [2] scan           rocPRIM exclusive scan                  -> segoff, T
@@ -156,6 +160,132 @@ __global__ void k_dust_zero(T *__restrict__ labels, uint64_t nvox,
     if (L != 0 && (uint64_t)counts[label_lookup(lh, (uint64_t)L)] < thr)
       labels[i] = 0;
   }
+}
+
+// ---------------------------------------------------------------------------
+// device label map (MeshTask remap_table / object_ids / exclude_object_ids,
+// reference mesh.py:200-204 and 357-369 via fastremap.mask_except / remap /
+// mask): the three options fold on the host into ONE {key -> val} table
+// plus a miss policy (igneous_amd/remap.py fold_label_ops); one volume pass
+// rewrites the resident labels in place after dust and before the count
+// pass. Each voxel is looked up once with its raw label (no chaining).
+
+struct MapTable {
+  ulonglong2 *slots;  // .x = key (0 = empty), .y = val
+  uint64_t nslots;    // power of two, >= 2n
+};
+
+// flag bits written by k_map_build
+#define MAP_ERR_DUPLICATE 1u
+#define MAP_ERR_FULL      2u
+
+__global__ void k_map_build(const uint64_t *__restrict__ keys,
+                            const uint64_t *__restrict__ vals, uint64_t n,
+                            MapTable t, uint32_t *__restrict__ err) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t key = keys[i];
+  uint64_t slot = mix64(key) & (t.nslots - 1);
+  for (uint64_t probe = 0; probe < t.nslots; ++probe) {
+    uint64_t prev = atomicCAS((unsigned long long *)&t.slots[slot].x, 0ull,
+                              (unsigned long long)key);
+    if (prev == 0) {  // claimed: this thread alone writes the value
+      t.slots[slot].y = vals[i];
+      return;
+    }
+    if (prev == key) {  // another entry holds the same key
+      atomicOr(err, MAP_ERR_DUPLICATE);
+      return;
+    }
+    slot = (slot + 1) & (t.nslots - 1);
+  }
+  atomicOr(err, MAP_ERR_FULL);
+}
+
+// One lookup. cl/cr are the lane's one-entry cache of its last
+// (label, result): runs along x share a label. cl starts at 0, which is
+// never looked up.
+template <typename T>
+__device__ __forceinline__ T map_one(T L, const MapTable &t, bool miss_zero,
+                                     T &cl, T &cr) {
+  if (L == 0) return 0;
+  if (L == cl) return cr;
+  T r = miss_zero ? (T)0 : L;
+  uint64_t slot = mix64((uint64_t)L) & (t.nslots - 1);
+  for (uint64_t probe = 0; probe < t.nslots; ++probe) {
+    ulonglong2 e = t.slots[slot];
+    if (e.x == (uint64_t)L) { r = (T)e.y; break; }
+    if (e.x == 0) break;
+    slot = (slot + 1) & (t.nslots - 1);
+  }
+  cl = L;
+  cr = r;
+  return r;
+}
+
+template <typename T> struct MapVec;
+template <> struct MapVec<uint64_t> { typedef ulonglong2 type; };
+template <> struct MapVec<uint32_t> { typedef uint4 type; };
+
+template <typename T>
+__device__ __forceinline__ void map_volume(T *__restrict__ labels,
+                                           uint64_t nvox, const MapTable &t,
+                                           uint32_t miss_zero) {
+  typedef typename MapVec<T>::type V;
+  constexpr int NV = 16 / sizeof(T);
+  const uint64_t nvec = nvox / NV;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
+  const bool mz = miss_zero != 0;
+  T cl = 0, cr = 0;
+  V *vp = reinterpret_cast<V *>(labels);  // hipMalloc base: 16-B aligned
+  for (uint64_t i = tid; i < nvec; i += nthr) {
+    union { V v; T e[NV]; } in, o;
+    in.v = vp[i];
+    bool changed = false;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      o.e[k] = map_one<T>(in.e[k], t, mz, cl, cr);
+      changed |= (o.e[k] != in.e[k]);
+    }
+    if (changed) vp[i] = o.v;
+  }
+  // scalar tail: nvox not a multiple of the vector width
+  const uint64_t i = nvec * NV + tid;
+  if (i < nvox) {
+    T L = labels[i];
+    T r = map_one<T>(L, t, mz, cl, cr);
+    if (r != L) labels[i] = r;
+  }
+}
+
+// table probed in HBM/L2: any size up to the cap
+template <typename T>
+__global__ void k_label_map(T *__restrict__ labels, uint64_t nvox,
+                            MapTable t, uint32_t miss_zero) {
+  map_volume<T>(labels, nvox, t, miss_zero);
+}
+
+// small tables (n <= MAP_LDS_MAX_ENTRIES, at most 4096 slots = 64 KB):
+// every workgroup stages the built table in LDS once and probes it there.
+// Under MISS_ZERO most labels MISS, and a miss walks to an empty slot
+// (~2.5 probes at load 0.5) — divergent 16-B requests that cost more than
+// the volume stream when they go to L2. 1024 threads x 64 KB keeps two
+// workgroups (32 waves) per CU.
+#define MAP_LDS_MAX_ENTRIES 2048u
+#define MAP_LDS_BLOCK 1024
+
+template <typename T>
+__global__ __launch_bounds__(MAP_LDS_BLOCK) void k_label_map_lds(
+    T *__restrict__ labels, uint64_t nvox, MapTable g, uint32_t miss_zero) {
+  extern __shared__ ulonglong2 s_map_tab[];
+  for (uint32_t i = threadIdx.x; i < (uint32_t)g.nslots; i += blockDim.x)
+    s_map_tab[i] = g.slots[i];
+  __syncthreads();
+  MapTable t;
+  t.slots = s_map_tab;
+  t.nslots = g.nslots;
+  map_volume<T>(labels, nvox, t, miss_zero);
 }
 
 // invert: label id -> label value (fill after count)
@@ -655,7 +785,8 @@ struct mg_ctx {
       simp_Q, simp_pick, simp_remap, simp_flab, simp_flab_alt,
       simp_faces_alt, simp_verts_alt, simp_vbase_alt, simp_meta, simp_ref,
       simp_keep, simp_keep_scan, simp_park, simp_first, simp_troff_final,
-      simp_deg, simp_adj, simp_rh, simp_sched, simp_accept;
+      simp_deg, simp_adj, simp_rh, simp_sched, simp_accept,
+      map_tab, map_keys, map_vals;  // label map table + staged pairs
   uint64_t lh_slots = 1ull << 20;
   HostBuf h_verts, h_faces;  // pinned output staging, reused across calls
   hipEvent_t ev[16] = {};
@@ -767,7 +898,8 @@ void mg_destroy(mg_ctx *c) {
                   &c->simp_meta, &c->simp_ref, &c->simp_keep,
                   &c->simp_keep_scan, &c->simp_park, &c->simp_first,
                   &c->simp_troff_final, &c->simp_deg, &c->simp_adj,
-                  &c->simp_rh, &c->simp_sched, &c->simp_accept}) {
+                  &c->simp_rh, &c->simp_sched, &c->simp_accept,
+                  &c->map_tab, &c->map_keys, &c->map_vals}) {
     if (b->ptr) (void)hipFree(b->ptr);
   }
   if (c->h_verts.ptr) (void)hipHostFree(c->h_verts.ptr);
@@ -801,14 +933,18 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            float rx, float ry, float rz,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
-                           uint32_t flags_,
+                           uint32_t flags_, const mg_label_map *map,
                            mg_meshset **out);
 
-int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
-                  int dtype, float rx, float ry, float rz,
-                  uint32_t reduction_factor, float max_error,
-                  int voxel_centered, uint64_t dust_threshold,
-                  uint32_t flags, mg_meshset **out) {
+// Label map table cap: above this the caller preprocesses on the host.
+#define MG_MAP_MAX_ENTRIES (1ull << 24)
+
+int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
+                         int sz, int dtype, float rx, float ry, float rz,
+                         uint32_t reduction_factor, float max_error,
+                         int voxel_centered, uint64_t dust_threshold,
+                         uint32_t flags, const mg_label_map *map,
+                         mg_meshset **out) {
   if (!c) { SET_ERR(c, "null ctx"); return 1; }
   std::lock_guard<std::mutex> g(c->lock);
   c->err.clear();
@@ -821,10 +957,55 @@ int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
     SET_ERR(c, "bad dtype %d", dtype);
     return 3;
   }
+  if (map) {
+    if (map->miss != MG_MAP_MISS_KEEP && map->miss != MG_MAP_MISS_ZERO) {
+      SET_ERR(c, "label map: bad miss policy %u", map->miss);
+      return 5;
+    }
+    if (flags & MG_FLAG_SKIP_H2D) {
+      SET_ERR(c, "label map cannot be combined with MG_FLAG_SKIP_H2D "
+              "(the resident volume is already mapped)");
+      return 5;
+    }
+    if (map->n > MG_MAP_MAX_ENTRIES) {
+      SET_ERR(c, "label map: %llu entries exceed the %llu-entry cap",
+              (unsigned long long)map->n,
+              (unsigned long long)MG_MAP_MAX_ENTRIES);
+      return 5;
+    }
+    if (map->n > 0 && (!map->keys || !map->vals)) {
+      SET_ERR(c, "label map: null keys/vals with n=%llu",
+              (unsigned long long)map->n);
+      return 5;
+    }
+    for (uint64_t i = 0; i < map->n; ++i) {
+      if (map->keys[i] == 0) {
+        SET_ERR(c, "label map: key 0 at entry %llu (label 0 is never "
+                "looked up)", (unsigned long long)i);
+        return 5;
+      }
+      if (dtype == MG_U32 && map->vals[i] > 0xFFFFFFFFull) {
+        SET_ERR(c, "label map: value %llu at entry %llu does not fit "
+                "MG_U32", (unsigned long long)map->vals[i],
+                (unsigned long long)i);
+        return 5;
+      }
+    }
+  }
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return mesh_chunk_impl(c, labels, sx, sy, sz, dtype, rx, ry, rz,
                          reduction_factor, max_error, voxel_centered,
-                         dust_threshold, flags, out);
+                         dust_threshold, flags, map, out);
+}
+
+int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
+                  int dtype, float rx, float ry, float rz,
+                  uint32_t reduction_factor, float max_error,
+                  int voxel_centered, uint64_t dust_threshold,
+                  uint32_t flags, mg_meshset **out) {
+  return mg_mesh_chunk_mapped(c, labels, sx, sy, sz, dtype, rx, ry, rz,
+                              reduction_factor, max_error, voxel_centered,
+                              dust_threshold, flags, nullptr, out);
 }
 
 }  // extern "C"
@@ -1455,7 +1636,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            float rx, float ry, float rz,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
-                           uint32_t flags_,
+                           uint32_t flags_, const mg_label_map *map,
                            mg_meshset **out) {
   const size_t esize = (dtype == MG_U64) ? 8 : 4;
   const uint64_t nvox = (uint64_t)sx * sy * sz;
@@ -1549,6 +1730,80 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
       HIP_TRY(c, hipGetLastError(), 16);
       break;
     }
+  }
+
+  // label map in place on the resident labels (after dust, which counted
+  // the RAW labels — the reference's order, mesh.py:193-204)
+  if (map) {
+    const uint64_t n = map->n;
+    MapTable mt;
+    mt.nslots = next_pow2_u64(std::max<uint64_t>(2 * n, 64));
+    if (ensure(c, c->map_tab, mt.nslots * 16)) return 41;
+    if (ensure(c, c->lh_misc, 256)) return 41;
+    mt.slots = (ulonglong2 *)c->map_tab.ptr;
+    uint32_t *d_err = (uint32_t *)c->lh_misc.ptr + 2;
+    HIP_TRY(c, hipEventRecord(c->ev[11], s), 41);
+    HIP_TRY(c, hipMemsetAsync(c->map_tab.ptr, 0, mt.nslots * 16, s), 41);
+    HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, s), 41);
+    if (n > 0) {
+      if (ensure(c, c->map_keys, n * 8)) return 41;
+      if (ensure(c, c->map_vals, n * 8)) return 41;
+      HIP_TRY(c, hipMemcpyAsync(c->map_keys.ptr, map->keys, n * 8,
+                                hipMemcpyHostToDevice, s), 41);
+      HIP_TRY(c, hipMemcpyAsync(c->map_vals.ptr, map->vals, n * 8,
+                                hipMemcpyHostToDevice, s), 41);
+      const int bblk = 256;
+      hipLaunchKernelGGL(k_map_build, dim3((uint32_t)((n + bblk - 1) / bblk)),
+                         dim3(bblk), 0, s, (const uint64_t *)c->map_keys.ptr,
+                         (const uint64_t *)c->map_vals.ptr, n, mt, d_err);
+    }
+    const uint64_t nvec = nvox / (16 / esize);
+    const uint32_t miss_zero = map->miss == MG_MAP_MISS_ZERO;
+    // MG_MAP_LDS=0 reverts small tables to the L2-probed kernel (A/B)
+    static const bool use_lds = []() {
+      const char *e = getenv("MG_MAP_LDS");
+      return !(e && e[0] == '0');
+    }();
+    if (use_lds && n <= MAP_LDS_MAX_ENTRIES) {
+      const int mblk = MAP_LDS_BLOCK;
+      const uint32_t mnb = (uint32_t)std::min<uint64_t>(
+          std::max<uint64_t>((nvec + mblk - 1) / mblk, 1), 512);
+      const size_t lds = mt.nslots * 16;  // <= 4096 slots = 64 KB
+      if (dtype == MG_U64)
+        hipLaunchKernelGGL(k_label_map_lds<uint64_t>, dim3(mnb), dim3(mblk),
+                           lds, s, (uint64_t *)c->labels.ptr, nvox, mt,
+                           miss_zero);
+      else
+        hipLaunchKernelGGL(k_label_map_lds<uint32_t>, dim3(mnb), dim3(mblk),
+                           lds, s, (uint32_t *)c->labels.ptr, nvox, mt,
+                           miss_zero);
+    } else {
+      const int mblk = 256;
+      const uint32_t mnb = (uint32_t)std::min<uint64_t>(
+          std::max<uint64_t>((nvec + mblk - 1) / mblk, 1), 4096);
+      if (dtype == MG_U64)
+        hipLaunchKernelGGL(k_label_map<uint64_t>, dim3(mnb), dim3(mblk), 0, s,
+                           (uint64_t *)c->labels.ptr, nvox, mt, miss_zero);
+      else
+        hipLaunchKernelGGL(k_label_map<uint32_t>, dim3(mnb), dim3(mblk), 0, s,
+                           (uint32_t *)c->labels.ptr, nvox, mt, miss_zero);
+    }
+    HIP_TRY(c, hipGetLastError(), 41);
+    HIP_TRY(c, hipEventRecord(c->ev[12], s), 41);
+    uint32_t map_err = 0;
+    HIP_TRY(c, hipMemcpyAsync(&map_err, d_err, 4, hipMemcpyDeviceToHost, s),
+            41);
+    HIP_TRY(c, hipStreamSynchronize(s), 41);
+    if (map_err & MAP_ERR_DUPLICATE) {
+      SET_ERR(c, "label map: duplicate key among %llu entries",
+              (unsigned long long)n);
+      return 42;
+    }
+    if (map_err) {
+      SET_ERR(c, "label map: table build failed (flag %u)", map_err);
+      return 42;
+    }
+    c->stats.ms_labelmap = ev_ms(c, 11, 12);
   }
 
   // label hash (grow-and-retry on overflow)

@@ -23,9 +23,16 @@ SO_PATH = os.path.join(_HERE, "csrc", "libmeshgine.so")
 MG_U32, MG_U64 = 0, 1
 MG_FLAG_DEVICE_ONLY = 1
 MG_FLAG_SKIP_H2D = 2
+MG_MAP_MISS_KEEP, MG_MAP_MISS_ZERO = 0, 1
+# mg_mesh_chunk_mapped's table cap: larger folds preprocess on the host
+LABEL_MAP_MAX_ENTRIES = 1 << 24
+# tables up to this many entries are probed from an LDS copy instead of
+# L2 (MAP_LDS_MAX_ENTRIES in csrc/meshgine.hip; tests straddle it)
+LABEL_MAP_LDS_MAX = 2048
 
 _EXPORTED_SYMBOLS = [
-    "mg_init", "mg_destroy", "mg_mesh_chunk", "mg_meshset_free",
+    "mg_init", "mg_destroy", "mg_mesh_chunk", "mg_mesh_chunk_mapped",
+    "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
 ]
 
@@ -56,6 +63,15 @@ class _MgMeshSet(ctypes.Structure):
     ]
 
 
+class _MgLabelMap(ctypes.Structure):
+    _fields_ = [
+        ("keys", ctypes.c_void_p),
+        ("vals", ctypes.c_void_p),
+        ("n", ctypes.c_uint64),
+        ("miss", ctypes.c_uint32),
+    ]
+
+
 class MgStats(ctypes.Structure):
     _fields_ = [
         ("ms_h2d", ctypes.c_double),
@@ -71,6 +87,7 @@ class MgStats(ctypes.Structure):
         ("total_verts", ctypes.c_uint64),
         ("n_labels", ctypes.c_uint64),
         ("bytes_read_algorithmic", ctypes.c_uint64),
+        ("ms_labelmap", ctypes.c_double),
     ]
 
     def as_dict(self) -> dict:
@@ -108,6 +125,11 @@ def load_library() -> ctypes.CDLL:
             ctypes.c_uint64, ctypes.c_uint32,
             ctypes.POINTER(ctypes.POINTER(_MgMeshSet)),
         ]
+        lib.mg_mesh_chunk_mapped.restype = ctypes.c_int
+        lib.mg_mesh_chunk_mapped.argtypes = (
+            lib.mg_mesh_chunk.argtypes[:-1]
+            + [ctypes.POINTER(_MgLabelMap)]
+            + lib.mg_mesh_chunk.argtypes[-1:])
         lib.mg_meshset_free.argtypes = [ctypes.POINTER(_MgMeshSet)]
         lib.mg_get_stats.restype = ctypes.c_int
         lib.mg_get_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(MgStats)]
@@ -171,10 +193,17 @@ class Engine:
                    device_only: bool = False,
                    skip_h2d: bool = False,
                    dust_threshold: int = 0,
-                   copy: bool = True) -> dict:
+                   copy: bool = True,
+                   label_map=None) -> dict:
         """GPU counterpart of oracle.mesh_chunk: F-order (sx,sy,sz)
         uint32/uint64 labels -> {label: (verts (V,3) f32 nm, faces (F,3) u32)},
         labels ascending. Under device_only returns {} (stats still filled).
+
+        label_map=(keys, vals, miss) as produced by remap.fold_label_ops
+        (miss 'keep' or 'zero') rewrites the labels ON DEVICE after dust
+        and before meshing (mg_mesh_chunk_mapped); the host array is not
+        touched. It cannot be combined with skip_h2d: the resident volume
+        is already mapped.
 
         copy=False returns VIEWS into this context's pinned staging
         buffers — zero host copies, but the arrays are only valid until
@@ -190,19 +219,43 @@ class Engine:
         sx, sy, sz = labels.shape
         flags = (MG_FLAG_DEVICE_ONLY if device_only else 0) | \
                 (MG_FLAG_SKIP_H2D if skip_h2d else 0)
+        args = (
+            self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
+            sx, sy, sz, dtype,
+            float(resolution[0]), float(resolution[1]), float(resolution[2]),
+            int(reduction_factor), float(max_error),
+            int(bool(voxel_centered)), int(dust_threshold), flags)
+        cmap = None
+        if label_map is not None:
+            if skip_h2d:
+                raise ValueError(
+                    "label_map cannot be combined with skip_h2d: the "
+                    "resident volume has already been mapped")
+            keys, vals, miss = label_map
+            if miss not in ('keep', 'zero'):
+                raise ValueError(f"label_map miss policy {miss!r}: "
+                                 f"expected 'keep' or 'zero'")
+            keys = np.ascontiguousarray(keys, dtype=np.uint64)
+            vals = np.ascontiguousarray(vals, dtype=np.uint64)
+            if keys.ndim != 1 or keys.shape != vals.shape:
+                raise ValueError("label_map keys/vals must be 1-D arrays "
+                                 "of equal length")
+            cmap = _MgLabelMap(
+                keys.ctypes.data, vals.ctypes.data, keys.shape[0],
+                MG_MAP_MISS_ZERO if miss == 'zero' else MG_MAP_MISS_KEEP)
         out = ctypes.POINTER(_MgMeshSet)()
         with self._lock:
-            rc = self.lib.mg_mesh_chunk(
-                self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
-                sx, sy, sz, dtype,
-                float(resolution[0]), float(resolution[1]), float(resolution[2]),
-                int(reduction_factor), float(max_error),
-                int(bool(voxel_centered)), int(dust_threshold), flags,
-                ctypes.byref(out))
+            if cmap is None:
+                fn = "mg_mesh_chunk"
+                rc = self.lib.mg_mesh_chunk(*args, ctypes.byref(out))
+            else:
+                fn = "mg_mesh_chunk_mapped"
+                rc = self.lib.mg_mesh_chunk_mapped(
+                    *args, ctypes.byref(cmap), ctypes.byref(out))
             if rc != 0:
                 err = self.lib.mg_last_error(self.ctx)
                 raise RuntimeError(
-                    f"mg_mesh_chunk failed rc={rc}: "
+                    f"{fn} failed rc={rc}: "
                     f"{err.decode() if err else 'unknown'}")
             result = {}
             try:
@@ -285,19 +338,23 @@ def mesh_chunk(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                reduction_factor: int = 0, max_error: float = 40.0,
                voxel_centered: bool = True, device_id: Optional[int] = None,
                dust_threshold: int = 0,
-               copy: bool = True) -> dict:
+               copy: bool = True, label_map=None) -> dict:
     """Module-level product mesher (the default MeshTask path)."""
     if device_id is None:
         device_id = int(os.environ.get("MESHGINE_DEVICE",
                                        os.environ.get("LOCAL_RANK", "0")))
     return Engine.get(device_id).mesh_chunk(
         labels, resolution, reduction_factor, max_error, voxel_centered,
-        dust_threshold=dust_threshold, copy=copy)
+        dust_threshold=dust_threshold, copy=copy, label_map=label_map)
 
 
 # MeshTask checks this to delegate dust_threshold preprocessing to the
 # device (three HIP volume passes) instead of a host numpy unique/mask
 mesh_chunk.handles_dust = True
+# ... and to hand it remap_table / object_ids / exclude_object_ids folded
+# into one label_map (remap.fold_label_ops) instead of the host numpy
+# mask_except/remap/mask sequence
+mesh_chunk.handles_label_map = True
 
 
 def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,

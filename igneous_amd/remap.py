@@ -49,6 +49,65 @@ def remap(data: np.ndarray, table: dict, in_place: bool = True) -> np.ndarray:
     return out
 
 
+def _ids(ids, what: str) -> set:
+    out = set()
+    for i in (ids if ids is not None else ()):
+        i = int(i)
+        if i < 0:
+            raise ValueError(f"{what}: negative id {i}")
+        out.add(i)
+    return out
+
+
+def fold_label_ops(remap_table, object_ids, exclude_object_ids, dtype):
+    """Fold MeshTask's three label-selection options, in the reference's
+    order remap -> object_ids -> exclude_object_ids (mesh.py:193-204), into
+    ONE lookup table for the engine's device label map.
+
+    Returns None when no option is set, else (keys u64[n], vals u64[n],
+    miss): each voxel is looked up once with its RAW label (no chaining);
+    a hit is replaced by its val (0 = erase), a label absent from the
+    table is kept (miss == 'keep') or erased (miss == 'zero'). Label 0 is
+    never a key. Applying the triple equals the host sequence
+    mask_except(keys) -> remap -> mask_except(object_ids) ->
+    mask(exclude_object_ids) above.
+
+    Negative ids and remap values that do not fit dtype raise ValueError;
+    keys that do not fit dtype can never match a voxel and are dropped."""
+    top = int(np.iinfo(np.dtype(dtype)).max)
+    only = _ids(object_ids, "object_ids")
+    excl = _ids(exclude_object_ids, "exclude_object_ids")
+
+    if remap_table is not None:
+        table = {}
+        for k, v in remap_table.items():
+            k, v = int(k), int(v)
+            if k < 0 or v < 0:
+                raise ValueError(f"remap_table: negative id in {k}: {v}")
+            if v > top:
+                raise ValueError(
+                    f"remap_table: value {v} does not fit {np.dtype(dtype)}")
+            if k == 0 or k > top:
+                continue  # the reference forces remap[0] = 0
+            if (only and v not in only) or v in excl:
+                v = 0
+            table[k] = v
+        miss = 'zero'
+    elif only:
+        table = {k: k for k in only - excl if 0 < k <= top}
+        miss = 'zero'
+    elif excl:
+        table = {k: 0 for k in excl if 0 < k <= top}
+        miss = 'keep'
+    else:
+        return None
+
+    keys = np.fromiter(sorted(table), dtype=np.uint64, count=len(table))
+    vals = np.fromiter((table[int(k)] for k in keys), dtype=np.uint64,
+                       count=len(table))
+    return keys, vals, miss
+
+
 def unique(data: np.ndarray, return_counts: bool = False):
     """fastremap.unique equivalent (mesh.py:318)."""
     return np.unique(data, return_counts=return_counts)

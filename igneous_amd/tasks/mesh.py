@@ -15,6 +15,10 @@ Mirrors the reference class at /root/reference/igneous/tasks/mesh/mesh.py:
 The compute crosses to the GPU exactly where the reference crosses into
 zmesh C++ (mesh.py:245 and mesh.py:374-381): one mg_mesh_chunk call on the
 HIP engine produces all labels' welded (and optionally simplified) meshes.
+dust_threshold and the label selection (remap_table / object_ids /
+exclude_object_ids, folded by remap.fold_label_ops) ride the same call as
+device volume passes when the mesher advertises handles_dust /
+handles_label_map.
 There is no CPU fallback; a missing engine raises.
 
 Deliberate deviations (documented in DESIGN.md):
@@ -174,24 +178,46 @@ class MeshTask(RegisteredTask):
         # a multi-second host unique/mask at 512^3); host fallback keeps
         # the reference semantics for injected CPU meshers
         mesher_probe = _get_mesher()
+
+        # label selection (remap_table / object_ids / exclude_object_ids):
+        # folded into ONE lookup table and applied by the engine in a
+        # device volume pass when the mesher advertises support; injected
+        # meshers — and folds above the engine's table cap — keep the
+        # host mask_except/remap/mask sequence
+        if opts['remap_table'] is not None:
+            opts['remap_table'] = {
+                int(k): int(v) for k, v in opts['remap_table'].items()}
+        label_map = None
+        if getattr(mesher_probe, 'handles_label_map', False):
+            label_map = fastremap_np.fold_label_ops(
+                opts['remap_table'], opts['object_ids'],
+                opts['exclude_object_ids'], data.dtype)
+            if label_map is not None:
+                from ..engine import LABEL_MAP_MAX_ENTRIES
+                if len(label_map[0]) > LABEL_MAP_MAX_ENTRIES:
+                    label_map = None
+
         device_dust = 0
         if (opts['dust_threshold'] and not opts['dust_global']
-                and opts['remap_table'] is None
+                and (opts['remap_table'] is None or label_map is not None)
                 and getattr(mesher_probe, 'handles_dust', False)):
-            # remap_table must force the HOST order: the reference dusts
+            # a HOST remap must force host dust: the reference dusts
             # BEFORE remapping (mesh.py:193-198), so labels merged by
-            # the remap pool their voxel counts — device dust runs after
-            # the host remap and would see the merged labels
+            # the remap pool their voxel counts — device dust would run
+            # after the host remap and see the merged labels. With the
+            # device label map the engine's order is dust -> map, the
+            # reference's order, so both run on the device.
             device_dust = int(opts['dust_threshold'])
         else:
             data = self._remove_dust(data, opts['dust_threshold'],
                                      opts['dust_global'])
-        data = self._remap(data)
 
-        if opts['object_ids']:
-            data = fastremap_np.mask_except(data, opts['object_ids'], in_place=True)
-        if opts['exclude_object_ids']:
-            data = fastremap_np.mask(data, opts['exclude_object_ids'], in_place=True)
+        if label_map is None:
+            data = self._remap(data)
+            if opts['object_ids']:
+                data = fastremap_np.mask_except(data, opts['object_ids'], in_place=True)
+            if opts['exclude_object_ids']:
+                data = fastremap_np.mask(data, opts['exclude_object_ids'], in_place=True)
 
         data = data[..., 0]
 
@@ -204,6 +230,8 @@ class MeshTask(RegisteredTask):
         extra = {}
         if device_dust:
             extra['dust_threshold'] = device_dust
+        if label_map is not None:
+            extra['label_map'] = label_map
         try:
             raw = mesher(
                 data,

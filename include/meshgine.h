@@ -19,12 +19,20 @@
  *                        (mesh.py:374-381: per-label quadric edge-collapse
  *                        simplification + welded vertex/face extraction).
  *                        One call produces every label's mesh.
+ *   mg_mesh_chunk_mapped — mg_mesh_chunk plus the label selection the
+ *                        reference runs on the host through fastremap
+ *                        ahead of the mesher: remap_table
+ *                        (mesh.py:357-369: mask_except to the table's keys,
+ *                        then remap) and object_ids / exclude_object_ids
+ *                        (mesh.py:200-204: mask_except, mask). The three
+ *                        fold into one {key -> val} table + a miss policy
+ *                        (mg_label_map) applied in one device volume pass.
  *   mg_meshset_free    — replaces Python GC of zmesh.Mesh objects.
  *   mg_last_error      — error text for the last failed call on this ctx.
  *
  * The caller (igneous_amd.tasks.MeshTask, via ctypes) keeps everything the
- * reference keeps in Python: download, padding, dust/remap/object-id
- * masking, the shift of vertices into global nm coordinates
+ * reference keeps in Python: download, padding, folding the
+ * remap/object-id options into an mg_label_map, the shift of vertices into global nm coordinates
  * (mesh.py:434-435), precomputed encoding (mesh.py:448) and upload.
  *
  * Vertices returned are CHUNK-LOCAL nm coordinates (float32), exactly as
@@ -114,7 +122,25 @@ typedef struct {
   uint64_t total_verts; /* before simplification */
   uint64_t n_labels;
   uint64_t bytes_read_algorithmic; /* sx*sy*sz * sizeof(label) */
+  double ms_labelmap;   /* label map: table upload + build + volume pass,
+                           after H2D/dust and before pass 1 (0 if no map;
+                           also inside ms_total) */
 } mg_stats;
+
+/* Label selection folded into one lookup table (replaces the host
+ * fastremap sequence of mesh.py:200-204 and 357-369). Every voxel is
+ * looked up ONCE with its raw label — no chaining: {a:b, b:c} sends a->b
+ * and b->c. Labels absent from the table follow the miss policy. Label 0
+ * is never looked up and stays 0. */
+#define MG_MAP_MISS_KEEP 0u   /* absent labels stay (exclude_object_ids) */
+#define MG_MAP_MISS_ZERO 1u   /* absent labels are erased (remap_table,
+                                 object_ids) */
+typedef struct {
+  const uint64_t *keys;   /* n distinct non-zero labels (host) */
+  const uint64_t *vals;   /* n replacement labels, 0 = erase   */
+  uint64_t        n;      /* 0 is valid                        */
+  uint32_t        miss;   /* MG_MAP_MISS_*                     */
+} mg_label_map;
 
 /* Create a context on HIP device device_id (0-based). Returns NULL on
  * failure (no device, no HIP). */
@@ -146,6 +172,24 @@ int mg_mesh_chunk(mg_ctx *ctx, const void *labels,
                   int voxel_centered, uint64_t dust_threshold,
                   uint32_t flags,
                   mg_meshset **out);
+
+/* mg_mesh_chunk with a label map (NULL = none, identical to
+ * mg_mesh_chunk). Device order: H2D -> dust passes (counting RAW labels,
+ * mesh.py:193-198) -> label map in place -> count/emit pipeline — the
+ * reference's dust -> remap -> object_ids -> exclude_object_ids order
+ * (mesh.py:193-204).
+ * Errors (non-zero return + mg_last_error, never a fault): a zero key, a
+ * duplicate key, miss outside MG_MAP_MISS_*, a value >= 2^32 with MG_U32,
+ * more than 2^24 entries, or a map combined with MG_FLAG_SKIP_H2D (the
+ * map is not idempotent on an already-mapped resident volume). */
+int mg_mesh_chunk_mapped(mg_ctx *ctx, const void *labels,
+                         int sx, int sy, int sz, int dtype,
+                         float rx, float ry, float rz,
+                         uint32_t reduction_factor, float max_error,
+                         int voxel_centered, uint64_t dust_threshold,
+                         uint32_t flags,
+                         const mg_label_map *map,
+                         mg_meshset **out);
 
 void mg_meshset_free(mg_meshset *ms);
 

@@ -630,7 +630,15 @@ __global__ __launch_bounds__(BLK) void k_weld_insert(
 // consecutive corners and ballots the flags into one u64 word. Vertex
 // ids then come from a word-granular scan + popcount instead of a full
 // per-element scan array.
-__global__ void k_weld_flag_bits(const uint32_t *__restrict__ slots_sorted,
+//
+// The pass keeps what it gathered: a corner that is NOT a first
+// occurrence has its entry of the slot-triple array overwritten in place
+// with its first stream position p = ~wminp[slot] (always < i), so
+// nothing after this pass reads wminp again. First occurrences keep the
+// slot (needed to decode the coordinates; their first position is i
+// itself). `bits` says which kind each entry is. Each thread writes only
+// the entry it read.
+__global__ void k_weld_flag_bits(uint32_t *__restrict__ corner_ent,
                                  const uint32_t *__restrict__ wminp,
                                  unsigned long long *__restrict__ bits,
                                  uint64_t ncorners, uint64_t nwords) {
@@ -640,8 +648,11 @@ __global__ void k_weld_flag_bits(const uint32_t *__restrict__ slots_sorted,
   uint32_t lane = (uint32_t)(gid & 63);
   uint64_t i = word * 64 + lane;
   bool flag = false;
-  if (i < ncorners)
-    flag = (wminp[slots_sorted[i]] == ~(uint32_t)i);
+  if (i < ncorners) {
+    uint32_t p = ~wminp[corner_ent[i]];
+    flag = (p == (uint32_t)i);
+    if (!flag) corner_ent[i] = p;
+  }
   unsigned long long m = __ballot(flag);
   if (lane == 0) bits[word] = m;
 }
@@ -667,47 +678,7 @@ __global__ void k_total_verts(const uint32_t *__restrict__ wscan,
   *out = wscan[nwords - 1] + (uint32_t)__popcll(bits[nwords - 1]);
 }
 
-// [5d] first occurrences: record vertex id in the table, write the vertex
-// (doubled coordinates = 2*cell + edge offset, decoded from the record)
-__global__ void k_weld_verts(const uint32_t *__restrict__ slots_sorted,
-                             const uint32_t *__restrict__ wscan,
-                             const unsigned long long *__restrict__ bits,
-                             const uint32_t *__restrict__ wminp,
-                             uint32_t *__restrict__ wvtx,
-                             float *__restrict__ verts,
-                             uint32_t usx, uint32_t usxy,
-                             float rx, float ry, float rz, float shift,
-                             uint64_t ntris) {
-  uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ntris) return;
-  const uint32_t s[3] = {slots_sorted[3 * t], slots_sorted[3 * t + 1],
-                         slots_sorted[3 * t + 2]};
-  #pragma unroll
-  for (int v = 0; v < 3; ++v) {
-    uint32_t i = (uint32_t)(3 * t + v);
-    uint32_t slot = s[v];
-    if (wminp[slot] != ~i) continue;
-    uint32_t vid = vtx_id_of(wscan, bits, i);
-    wvtx[slot] = vid;
-    // doubled coordinates decoded from the slot (first occurrences
-    // only, ~1/6 of corners): slot = (lin*3 + axis)*2 | side
-    uint32_t eslot = slot >> 1;
-    uint32_t axis = eslot % 3u;
-    uint32_t lin = eslot / 3u;
-    uint32_t vz = lin / usxy;
-    uint32_t rem = lin - vz * usxy;
-    uint32_t vy = rem / usx;
-    uint32_t vx = rem - vy * usx;
-    float dx = (float)(2 * vx + (axis == 0));
-    float dy = (float)(2 * vy + (axis == 1));
-    float dz = (float)(2 * vz + (axis == 2));
-    verts[3ull * vid + 0] = (0.5f * dx + shift) * rx;
-    verts[3ull * vid + 1] = (0.5f * dy + shift) * ry;
-    verts[3ull * vid + 2] = (0.5f * dz + shift) * rz;
-  }
-}
-
-// [5e] per-label vertex bases: vbase[l] = vtx_scan at the label's first corner
+// [5d] per-label vertex bases: vbase[l] = vtx_scan at the label's first corner
 __global__ void k_vbase(const uint32_t *__restrict__ tri_off,
                         const uint32_t *__restrict__ wscan,
                         const unsigned long long *__restrict__ bits,
@@ -719,20 +690,70 @@ __global__ void k_vbase(const uint32_t *__restrict__ tri_off,
   else vbase[l] = vtx_id_of(wscan, bits, 3ull * tri_off[l]);
 }
 
-// [5f] faces: per-label local vertex indices (label id from the sorted
-// label array — the partition sort's key output)
-__global__ void k_faces(const uint32_t *__restrict__ slots_sorted,
-                        const uint32_t *__restrict__ lab_sorted,
-                        const uint32_t *__restrict__ wvtx,
-                        const uint32_t *__restrict__ vbase,
-                        uint32_t *__restrict__ faces,
-                        uint64_t ntris) {
+// [5e] vertices + faces in one pass, one thread per triangle. A corner's
+// vertex id is a pure function of its first stream position p:
+// wscan[p>>6] + popc(bits[p>>6] below bit p&63). A flagged corner (first
+// occurrence, ~1/6 of corners) is its own first position: it takes the id
+// from its own word, decodes the coordinates from the slot its entry
+// still holds and writes the vertex. An unflagged corner's entry holds p
+// (stored by the flag pass); a label's corners are contiguous in the
+// stream, so that bits/wscan lookup (12 B per 64 corners) is cache-local.
+// No vertex-id table: faces need nothing the vertex writes produce.
+// Label id from the sorted label array — the partition sort's key output.
+__global__ void k_weld_verts_faces(const uint32_t *__restrict__ corner_ent,
+                                   const uint32_t *__restrict__ lab_sorted,
+                                   const uint32_t *__restrict__ wscan,
+                                   const unsigned long long *__restrict__ bits,
+                                   const uint32_t *__restrict__ vbase,
+                                   float *__restrict__ verts,
+                                   uint32_t *__restrict__ faces,
+                                   uint32_t usx, uint32_t usxy,
+                                   float rx, float ry, float rz, float shift,
+                                   uint64_t ntris) {
   uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntris) return;
-  uint32_t base = vbase[lab_sorted[t]];
-  faces[3 * t + 0] = wvtx[slots_sorted[3 * t]] - base;
-  faces[3 * t + 1] = wvtx[slots_sorted[3 * t + 1]] - base;
-  faces[3 * t + 2] = wvtx[slots_sorted[3 * t + 2]] - base;
+  const uint32_t e[3] = {corner_ent[3 * t], corner_ent[3 * t + 1],
+                         corner_ent[3 * t + 2]};
+  const uint32_t base = vbase[lab_sorted[t]];
+  // corners 3t..3t+2 straddle two words when they start at bit 62 or 63
+  // (3 does not divide 64); the second word exists since 3t+2 < 3*ntris
+  const uint64_t w0 = (3 * t) >> 6;
+  const uint32_t b0 = (uint32_t)((3 * t) & 63);
+  const bool straddle = b0 > 61;
+  const unsigned long long word0 = bits[w0];
+  const uint32_t scan0 = wscan[w0];
+  const unsigned long long word1 = straddle ? bits[w0 + 1] : 0ull;
+  const uint32_t scan1 = straddle ? wscan[w0 + 1] : 0u;
+  #pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    uint32_t b = b0 + v;
+    const bool second = b > 63;
+    const unsigned long long word = second ? word1 : word0;
+    b &= 63;
+    uint32_t vid;
+    if ((word >> b) & 1ull) {
+      vid = (second ? scan1 : scan0) +
+            (uint32_t)__popcll(word & ((1ull << b) - 1));
+      // doubled coordinates decoded from the slot (first occurrences
+      // only): slot = (lin*3 + axis)*2 | side
+      uint32_t eslot = e[v] >> 1;
+      uint32_t axis = eslot % 3u;
+      uint32_t lin = eslot / 3u;
+      uint32_t vz = lin / usxy;
+      uint32_t rem = lin - vz * usxy;
+      uint32_t vy = rem / usx;
+      uint32_t vx = rem - vy * usx;
+      float dx = (float)(2 * vx + (axis == 0));
+      float dy = (float)(2 * vy + (axis == 1));
+      float dz = (float)(2 * vz + (axis == 2));
+      verts[3ull * vid + 0] = (0.5f * dx + shift) * rx;
+      verts[3ull * vid + 1] = (0.5f * dy + shift) * ry;
+      verts[3ull * vid + 2] = (0.5f * dz + shift) * rz;
+    } else {
+      vid = vtx_id_of(wscan, bits, e[v]);
+    }
+    faces[3 * t + v] = vid - base;
+  }
 }
 
 __global__ void k_iota(uint32_t *p, uint64_t n) {
@@ -779,7 +800,7 @@ struct mg_ctx {
       lh_keys, lh_vals, lh_misc,
       tri_label, tri_label_alt, order, order_alt, tri_keys, keys_sorted,
       tri_off, sort_tmp,
-      wh_keys, wh_vtx, vtx_scan, verts, faces, vbase,
+      wh_keys, vtx_scan, verts, faces, vbase,
       label_values,
       simp_fq, simp_valid, simp_pk, simp_pk_alt, simp_pv, simp_pv_alt,
       simp_Q, simp_pick, simp_remap, simp_flab, simp_flab_alt,
@@ -889,7 +910,7 @@ void mg_destroy(mg_ctx *c) {
                   &c->lh_keys, &c->lh_vals, &c->lh_misc, &c->tri_label,
                   &c->tri_label_alt, &c->order, &c->order_alt, &c->tri_keys,
                   &c->keys_sorted, &c->tri_off, &c->sort_tmp, &c->wh_keys,
-                  &c->wh_vtx, &c->vtx_scan,
+                  &c->vtx_scan,
                   &c->verts, &c->faces, &c->vbase, &c->label_values,
                   &c->simp_fq, &c->simp_valid, &c->simp_pk, &c->simp_pk_alt,
                   &c->simp_pv, &c->simp_pv_alt, &c->simp_Q, &c->simp_pick,
@@ -1984,12 +2005,11 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
   }
   uint64_t total_verts = 0;
   if (ensure(c, c->wh_keys, wslots * 4)) return 20;   // wminp
-  if (ensure(c, c->wh_vtx, wslots * 4)) return 20;    // wvtx
   if (ensure(c, c->vtx_scan, NC * 4)) return 20;
   HIP_TRY(c, hipMemsetAsync(c->wh_keys.ptr, 0, wslots * 4, s), 20);
   uint32_t *wminp = (uint32_t *)c->wh_keys.ptr;
-  uint32_t *wvtx = (uint32_t *)c->wh_vtx.ptr;
-  const uint32_t *slots_sorted = slots_out;
+  // slot triples; the flag pass turns non-first entries into first positions
+  uint32_t *corner_ent = slots_out;
   {
     int blk = 256;
     uint64_t nbt = (T + blk - 1) / blk;
@@ -2023,7 +2043,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
     {
       uint64_t nbw = (nwords * 64 + blk - 1) / blk;
       hipLaunchKernelGGL(k_weld_flag_bits, dim3((uint32_t)nbw), dim3(blk),
-                         0, s, slots_sorted, wminp, bits, NC, nwords);
+                         0, s, corner_ent, wminp, bits, NC, nwords);
     }
     auto it = rocprim::make_transform_iterator(bits, PopcWord{});
     size_t tmp_bytes = 0;
@@ -2058,20 +2078,18 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
     const unsigned long long *bits =
         (const unsigned long long *)c->vtx_scan.ptr;
     const uint32_t *wscan = (const uint32_t *)c->vtx_scan.ptr + 2 * nwords;
-    hipLaunchKernelGGL(k_weld_verts, dim3((uint32_t)nbt), dim3(blk), 0, s,
-                       slots_sorted, wscan, bits, wminp, wvtx,
-                       (float *)c->verts.ptr,
-                       (uint32_t)g.sx, (uint32_t)(g.sx * g.sy),
-                       rx, ry, rz, shift, T);
+    // vbase depends only on the scan, so it goes first
     uint32_t nbl = (nlabels + 1 + 255) / 256;
     hipLaunchKernelGGL(k_vbase, dim3(nbl), dim3(256), 0, s,
                        (const uint32_t *)c->tri_off.ptr,
                        wscan, bits,
                        (uint32_t *)c->vbase.ptr, nlabels, total_verts);
-    hipLaunchKernelGGL(k_faces, dim3((uint32_t)nbt), dim3(blk), 0, s,
-                       slots_sorted, lab_sorted, wvtx,
+    hipLaunchKernelGGL(k_weld_verts_faces, dim3((uint32_t)nbt), dim3(blk), 0,
+                       s, corner_ent, lab_sorted, wscan, bits,
                        (const uint32_t *)c->vbase.ptr,
-                       (uint32_t *)c->faces.ptr, T);
+                       (float *)c->verts.ptr, (uint32_t *)c->faces.ptr,
+                       (uint32_t)g.sx, (uint32_t)(g.sx * g.sy),
+                       rx, ry, rz, shift, T);
   }
   HIP_TRY(c, hipGetLastError(), 22);
   HIP_TRY(c, hipEventRecord(c->ev[6], s), 22);

@@ -7,6 +7,7 @@ tasks, and create_meshing_tasks. Compute runs as hand-written HIP/CDNA4
 kernels behind the C ABI in include/meshgine.h.
 """
 from .mesher import Mesher, simplify_fqmr, chunk_mesh
+from .engine import fill_holes
 from .meshes import Mesh
 from .queue import LocalTaskQueue, RegisteredTask
 from .tasks import (

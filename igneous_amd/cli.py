@@ -73,11 +73,15 @@ def mesh():
               help="mesh only this comma separated list of labels")
 @click.option("--exclude-labels", default=None, callback=_int_list,
               help="do not mesh labels in this comma separated list")
+@click.option("--fill-holes", default=0, type=int,
+              help="0: off. 1: fill enclosed holes in each label. 2: also "
+                   "fill holes open to a chunk face (2-D fill of the six "
+                   "border slices first). Levels >= 3 are not implemented")
 @click.option("--no-execute", is_flag=True, default=False,
               help="only create tasks + mesh info; do not run them")
 def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
           mesh_dir, compress, spatial_index, sharded, fill_missing,
-          closed_edge, labels, exclude_labels, no_execute):
+          closed_edge, labels, exclude_labels, fill_holes, no_execute):
     """(Re)Generate meshes for the segmentation at PATH
     (reference mesh_forge, cli.py:1035-1071)."""
     tasks = create_meshing_tasks(
@@ -93,6 +97,7 @@ def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
         closed_dataset_edges=closed_edge,
         object_ids=labels,
         exclude_object_ids=(exclude_labels or []),
+        fill_holes=fill_holes,
     )
     click.echo(f"{len(tasks)} MeshTasks over {path}")
     if no_execute:

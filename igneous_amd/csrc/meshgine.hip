@@ -16,7 +16,9 @@
 //   [0] (optional) k_dust_*: zero labels below dust_threshold;
 //       (optional, mg_mesh_chunk_mapped) k_map_build + k_label_map:
 //       remap_table / object_ids / exclude_object_ids as one table lookup
-//       per voxel, in place
+//       per voxel, in place;
+//       (optional, mg_mesh_chunk_filled) fill_holes.hip: hole filling by
+//       union-find rounds, hole volume kept resident for mg_mesh_holes
 //   [1] k_count        wave-per-64-cell-segment triangle counts
 //                      (+ label hash build)                    -> segcnt
 //   [2] scan           rocPRIM exclusive scan                  -> segoff, T
@@ -807,7 +809,14 @@ struct mg_ctx {
       simp_faces_alt, simp_verts_alt, simp_vbase_alt, simp_meta, simp_ref,
       simp_keep, simp_keep_scan, simp_park, simp_first, simp_troff_final,
       simp_deg, simp_adj, simp_rh, simp_sched, simp_accept,
-      map_tab, map_keys, map_vals;  // label map table + staged pairs
+      map_tab, map_keys, map_vals,  // label map table + staged pairs
+      // fill_holes: u32 working volume, union-find parents, per-root
+      // neighbour min/max, rewrite counter, resident hole volume
+      fill_vol, fill_parent, fill_cmin, fill_cmax, fill_misc, holes;
+  // hole volume stashed by the last mg_mesh_chunk_filled (mg_mesh_holes
+  // consumes it)
+  bool holes_valid = false;
+  int holes_sx = 0, holes_sy = 0, holes_sz = 0, holes_dtype = 0;
   uint64_t lh_slots = 1ull << 20;
   HostBuf h_verts, h_faces;  // pinned output staging, reused across calls
   hipEvent_t ev[16] = {};
@@ -870,6 +879,8 @@ static int ensure(mg_ctx *c, DevBuf &b, size_t bytes) {
   return 0;
 }
 
+#include "fill_holes.hip"
+
 extern "C" {
 
 const char *mg_version(void) { return "meshgine 0.1.0 (gfx950)"; }
@@ -920,7 +931,9 @@ void mg_destroy(mg_ctx *c) {
                   &c->simp_keep_scan, &c->simp_park, &c->simp_first,
                   &c->simp_troff_final, &c->simp_deg, &c->simp_adj,
                   &c->simp_rh, &c->simp_sched, &c->simp_accept,
-                  &c->map_tab, &c->map_keys, &c->map_vals}) {
+                  &c->map_tab, &c->map_keys, &c->map_vals,
+                  &c->fill_vol, &c->fill_parent, &c->fill_cmin,
+                  &c->fill_cmax, &c->fill_misc, &c->holes}) {
     if (b->ptr) (void)hipFree(b->ptr);
   }
   if (c->h_verts.ptr) (void)hipHostFree(c->h_verts.ptr);
@@ -955,21 +968,32 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
                            uint32_t flags_, const mg_label_map *map,
-                           mg_meshset **out);
+                           uint32_t fill_level, mg_meshset **out);
 
 // Label map table cap: above this the caller preprocesses on the host.
 #define MG_MAP_MAX_ENTRIES (1ull << 24)
 
-int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
+int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
                          int sz, int dtype, float rx, float ry, float rz,
                          uint32_t reduction_factor, float max_error,
                          int voxel_centered, uint64_t dust_threshold,
                          uint32_t flags, const mg_label_map *map,
-                         mg_meshset **out) {
+                         uint32_t fill_level, mg_meshset **out) {
   if (!c) { SET_ERR(c, "null ctx"); return 1; }
   std::lock_guard<std::mutex> g(c->lock);
   c->err.clear();
+  if (fill_level > 2) {
+    SET_ERR(c, "fill_level %u: only levels 0-2 are implemented (level 3 "
+            "needs a multilabel dilation, 4+ a merge threshold)", fill_level);
+    return 6;
+  }
+  if (fill_level && (flags & MG_FLAG_SKIP_H2D)) {
+    SET_ERR(c, "fill_holes cannot be combined with MG_FLAG_SKIP_H2D (the "
+            "resident volume is already filled)");
+    return 6;
+  }
   if (!labels || !out) { SET_ERR(c, "null argument"); return 1; }
+  c->holes_valid = false;  // a stash belongs to the call just before
   if (sx < 1 || sy < 1 || sz < 1 || sx > 2047 || sy > 2047 || sz > 2047) {
     SET_ERR(c, "dims out of range (1..2047): %d %d %d", sx, sy, sz);
     return 2;
@@ -1016,7 +1040,83 @@ int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return mesh_chunk_impl(c, labels, sx, sy, sz, dtype, rx, ry, rz,
                          reduction_factor, max_error, voxel_centered,
-                         dust_threshold, flags, map, out);
+                         dust_threshold, flags, map, fill_level, out);
+}
+
+int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
+                         int sz, int dtype, float rx, float ry, float rz,
+                         uint32_t reduction_factor, float max_error,
+                         int voxel_centered, uint64_t dust_threshold,
+                         uint32_t flags, const mg_label_map *map,
+                         mg_meshset **out) {
+  return mg_mesh_chunk_filled(c, labels, sx, sy, sz, dtype, rx, ry, rz,
+                              reduction_factor, max_error, voxel_centered,
+                              dust_threshold, flags, map, 0u, out);
+}
+
+int mg_mesh_holes(mg_ctx *c, float rx, float ry, float rz,
+                  uint32_t reduction_factor, float max_error,
+                  int voxel_centered, uint32_t flags, mg_meshset **out) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (!out) { SET_ERR(c, "null argument"); return 1; }
+  if (!c->holes_valid) {
+    SET_ERR(c, "mg_mesh_holes: no hole volume on this ctx (it is left by "
+            "mg_mesh_chunk_filled with fill_level > 0 and consumed by one "
+            "mg_mesh_holes call)");
+    return 7;
+  }
+  c->holes_valid = false;  // consumed, also on failure below
+  HIP_TRY(c, hipSetDevice(c->device), 4);
+  // the hole volume becomes the resident label volume: no upload
+  std::swap(c->labels, c->holes);
+  return mesh_chunk_impl(c, nullptr, c->holes_sx, c->holes_sy, c->holes_sz,
+                         c->holes_dtype, rx, ry, rz, reduction_factor,
+                         max_error, voxel_centered, 0,
+                         (flags & MG_FLAG_DEVICE_ONLY) | MG_FLAG_SKIP_H2D,
+                         nullptr, 0u, out);
+}
+
+int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,
+                  int dtype, uint32_t level, void *filled_out,
+                  void *holes_out, uint32_t *rounds_out) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (!labels || !filled_out || !holes_out) {
+    SET_ERR(c, "null argument");
+    return 1;
+  }
+  if (sx < 1 || sy < 1 || sz < 1 || sx > 2047 || sy > 2047 || sz > 2047) {
+    SET_ERR(c, "dims out of range (1..2047): %d %d %d", sx, sy, sz);
+    return 2;
+  }
+  if (dtype != MG_U32 && dtype != MG_U64) {
+    SET_ERR(c, "bad dtype %d", dtype);
+    return 3;
+  }
+  if (level < 1 || level > 2) {
+    SET_ERR(c, "fill level %u: only levels 1-2 are implemented (level 3 "
+            "needs a multilabel dilation, 4+ a merge threshold)", level);
+    return 6;
+  }
+  HIP_TRY(c, hipSetDevice(c->device), 4);
+  const size_t bytes = (size_t)sx * sy * sz * (dtype == MG_U64 ? 8 : 4);
+  c->holes_valid = false;  // c->holes is overwritten
+  if (ensure(c, c->labels, bytes)) return 11;
+  HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels, bytes,
+                            hipMemcpyHostToDevice, c->stream), 11);
+  uint32_t rounds = 0;
+  int rc = run_fill_holes(c, dtype, sx, sy, sz, level, &rounds);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(filled_out, c->labels.ptr, bytes,
+                            hipMemcpyDeviceToHost, c->stream), 55);
+  HIP_TRY(c, hipMemcpyAsync(holes_out, c->holes.ptr, bytes,
+                            hipMemcpyDeviceToHost, c->stream), 55);
+  HIP_TRY(c, hipStreamSynchronize(c->stream), 55);
+  if (rounds_out) *rounds_out = rounds;
+  return 0;
 }
 
 int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
@@ -1658,7 +1758,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
                            uint32_t flags_, const mg_label_map *map,
-                           mg_meshset **out) {
+                           uint32_t fill_level, mg_meshset **out) {
   const size_t esize = (dtype == MG_U64) ? 8 : 4;
   const uint64_t nvox = (uint64_t)sx * sy * sz;
   GridDims g;
@@ -1679,6 +1779,11 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
     mg_meshset *ms = (mg_meshset *)calloc(
         1, sizeof(mg_meshset) + 2 * sizeof(void *));
     *out = ms;
+    if (fill_level) {  // nothing to mesh in the hole volume either
+      c->holes_valid = true;
+      c->holes_sx = sx; c->holes_sy = sy; c->holes_sz = sz;
+      c->holes_dtype = dtype;
+    }
     return 0;
   }
 
@@ -1827,6 +1932,19 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
     c->stats.ms_labelmap = ev_ms(c, 11, 12);
   }
 
+  // fill_holes on the dusted + mapped labels (mesh.py:211-228): the
+  // resident volume becomes the filled one, the hole volume stays in
+  // c->holes for mg_mesh_holes
+  if (fill_level) {
+    HIP_TRY(c, hipEventRecord(c->ev[13], s), 56);
+    int frc = run_fill_holes(c, dtype, sx, sy, sz, fill_level, nullptr);
+    if (frc) return frc;
+    HIP_TRY(c, hipEventRecord(c->ev[14], s), 56);
+    c->holes_valid = true;
+    c->holes_sx = sx; c->holes_sy = sy; c->holes_sz = sz;
+    c->holes_dtype = dtype;
+  }
+
   // label hash (grow-and-retry on overflow)
   uint64_t total_tris = 0;
   uint32_t nlabels = 0;
@@ -1885,6 +2003,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
     *out = ms;
     HIP_TRY(c, hipStreamSynchronize(s), 14);
     c->stats.ms_h2d = ev_ms(c, 0, 1);
+    if (fill_level) c->stats.ms_fill = ev_ms(c, 13, 14);
     return 0;
   }
   if (total_tris > (1ull << 31) / 3 * 2) {  // 3T must fit u32 stream index
@@ -2178,6 +2297,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
   c->stats.ms_simplify = ev_ms(c, 6, 8);
   c->stats.ms_d2h = ev_ms(c, 8, 7);
   c->stats.ms_total = ev_ms(c, 0, 7);
+  if (fill_level) c->stats.ms_fill = ev_ms(c, 13, 14);
   return 0;
 }
 

@@ -32,6 +32,7 @@ LABEL_MAP_LDS_MAX = 2048
 
 _EXPORTED_SYMBOLS = [
     "mg_init", "mg_destroy", "mg_mesh_chunk", "mg_mesh_chunk_mapped",
+    "mg_mesh_chunk_filled", "mg_mesh_holes", "mg_fill_holes",
     "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
 ]
@@ -91,7 +92,20 @@ class MgStats(ctypes.Structure):
     ]
 
     def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _t in self._fields_}
+        out = {}
+        for klass in reversed(type(self).__mro__):
+            for name, _t in klass.__dict__.get("_fields_", ()):
+                out[name] = getattr(self, name)
+        return out
+
+
+class MgStatsFill(MgStats):
+    """mg_stats as the engine writes it now: the MgStats prefix plus the
+    fields appended after it (a ctypes subclass lays its own fields out
+    behind the base's, which is how the C struct grew)."""
+    _fields_ = [
+        ("ms_fill", ctypes.c_double),
+    ]
 
 
 _lib = None
@@ -130,9 +144,29 @@ def load_library() -> ctypes.CDLL:
             lib.mg_mesh_chunk.argtypes[:-1]
             + [ctypes.POINTER(_MgLabelMap)]
             + lib.mg_mesh_chunk.argtypes[-1:])
+        lib.mg_mesh_chunk_filled.restype = ctypes.c_int
+        lib.mg_mesh_chunk_filled.argtypes = (
+            lib.mg_mesh_chunk.argtypes[:-1]
+            + [ctypes.POINTER(_MgLabelMap), ctypes.c_uint32]
+            + lib.mg_mesh_chunk.argtypes[-1:])
+        lib.mg_mesh_holes.restype = ctypes.c_int
+        lib.mg_mesh_holes.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_float, ctypes.c_float, ctypes.c_float,
+            ctypes.c_uint32, ctypes.c_float, ctypes.c_int, ctypes.c_uint32,
+            ctypes.POINTER(ctypes.POINTER(_MgMeshSet)),
+        ]
+        lib.mg_fill_holes.restype = ctypes.c_int
+        lib.mg_fill_holes.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_uint32),
+        ]
         lib.mg_meshset_free.argtypes = [ctypes.POINTER(_MgMeshSet)]
         lib.mg_get_stats.restype = ctypes.c_int
-        lib.mg_get_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(MgStats)]
+        lib.mg_get_stats.argtypes = [ctypes.c_void_p,
+                                     ctypes.POINTER(MgStatsFill)]
         lib.mg_last_error.restype = ctypes.c_char_p
         lib.mg_last_error.argtypes = [ctypes.c_void_p]
         lib.mg_device_count.restype = ctypes.c_int
@@ -170,6 +204,9 @@ class Engine:
         self.lib = lib
         self.device_id = int(device_id)
         self._lock = threading.Lock()
+        # mg_stats of the last fill_holes meshing's FIRST call (the hole
+        # meshing that follows overwrites the ctx's stats)
+        self.last_fill_stats = None
         self.ctx = lib.mg_init(self.device_id)
         if not self.ctx:
             raise RuntimeError(
@@ -194,7 +231,8 @@ class Engine:
                    skip_h2d: bool = False,
                    dust_threshold: int = 0,
                    copy: bool = True,
-                   label_map=None) -> dict:
+                   label_map=None,
+                   fill_holes: int = 0):
         """GPU counterpart of oracle.mesh_chunk: F-order (sx,sy,sz)
         uint32/uint64 labels -> {label: (verts (V,3) f32 nm, faces (F,3) u32)},
         labels ascending. Under device_only returns {} (stats still filled).
@@ -208,7 +246,26 @@ class Engine:
         copy=False returns VIEWS into this context's pinned staging
         buffers — zero host copies, but the arrays are only valid until
         the next mesh_chunk on this Engine. Use when results are consumed
-        (encoded/written) before the next call, as MeshTask does."""
+        (encoded/written) before the next call, as MeshTask does.
+
+        fill_holes=1|2 fills holes ON DEVICE after dust and the label map
+        (mg_mesh_chunk_filled, contract in DESIGN.md §7) and returns the
+        PAIR (filled_meshes, hole_meshes): the meshes of the filled volume
+        and of the hole volume (mg_mesh_holes, no second upload). Both
+        dicts own their storage whatever `copy` says — the second meshing
+        reuses the first one's staging. Not combinable with skip_h2d."""
+        fill_holes = int(fill_holes)
+        if fill_holes < 0 or fill_holes > 2:
+            raise NotImplementedError(
+                f"fill_holes={fill_holes}: the engine implements levels "
+                f"1-2; level 3 needs a multilabel dilation and levels >= 4 "
+                f"a merge threshold")
+        if fill_holes and skip_h2d:
+            raise ValueError(
+                "fill_holes cannot be combined with skip_h2d: the "
+                "resident volume has already been filled")
+        if fill_holes:
+            copy = True
         labels = np.asfortranarray(labels)
         if labels.dtype == np.uint32:
             dtype = MG_U32
@@ -243,9 +300,14 @@ class Engine:
             cmap = _MgLabelMap(
                 keys.ctypes.data, vals.ctypes.data, keys.shape[0],
                 MG_MAP_MISS_ZERO if miss == 'zero' else MG_MAP_MISS_KEEP)
-        out = ctypes.POINTER(_MgMeshSet)()
         with self._lock:
-            if cmap is None:
+            out = ctypes.POINTER(_MgMeshSet)()
+            if fill_holes:
+                fn = "mg_mesh_chunk_filled"
+                rc = self.lib.mg_mesh_chunk_filled(
+                    *args, ctypes.byref(cmap) if cmap is not None else None,
+                    fill_holes, ctypes.byref(out))
+            elif cmap is None:
                 fn = "mg_mesh_chunk"
                 rc = self.lib.mg_mesh_chunk(*args, ctypes.byref(out))
             else:
@@ -257,47 +319,103 @@ class Engine:
                 raise RuntimeError(
                     f"{fn} failed rc={rc}: "
                     f"{err.decode() if err else 'unknown'}")
-            result = {}
-            try:
-                ms = out.contents
-                n = int(ms.nmeshes)
-                if n:
-                    # one GIL-releasing memmove per flat buffer (the flat
-                    # buffers are ctx-owned pinned staging, valid until
-                    # the next call on this ctx), then per-label views
-                    tv, tt = int(ms.total_verts), int(ms.total_tris)
-                    if copy:
-                        all_v = np.empty((tv, 3), dtype=np.float32)
-                        all_f = np.empty((tt, 3), dtype=np.uint32)
-                        if tv:
-                            ctypes.memmove(all_v.ctypes.data, ms.verts_base,
-                                           tv * 12)
-                        if tt:
-                            ctypes.memmove(all_f.ctypes.data, ms.faces_base,
-                                           tt * 12)
-                    else:
-                        all_v = np.ctypeslib.as_array(
-                            ms.verts_base, shape=(max(tv, 1), 3))[:tv]
-                        all_f = np.ctypeslib.as_array(
-                            ms.faces_base, shape=(max(tt, 1), 3))[:tt]
-                    labels = np.ctypeslib.as_array(
-                        ms.labels_arr, shape=(n,)).tolist()
-                    voff = np.ctypeslib.as_array(
-                        ms.voff_arr, shape=(n,)).tolist()
-                    nv = np.ctypeslib.as_array(
-                        ms.nv_arr, shape=(n,)).tolist()
-                    foff = np.ctypeslib.as_array(
-                        ms.foff_arr, shape=(n,)).tolist()
-                    nf = np.ctypeslib.as_array(
-                        ms.nf_arr, shape=(n,)).tolist()
-                    result = {
-                        lab: (all_v[vo:vo + kv], all_f[fo:fo + kf])
-                        for lab, vo, kv, fo, kf
-                        in zip(labels, voff, nv, foff, nf)
-                    }
-            finally:
-                self.lib.mg_meshset_free(out)
+            result = self._collect(out, copy)
+            if not fill_holes:
+                return result
+            self.last_fill_stats = self.stats()
+            out = ctypes.POINTER(_MgMeshSet)()
+            rc = self.lib.mg_mesh_holes(
+                self.ctx, *args[6:12], flags & MG_FLAG_DEVICE_ONLY,
+                ctypes.byref(out))
+            if rc != 0:
+                err = self.lib.mg_last_error(self.ctx)
+                raise RuntimeError(
+                    f"mg_mesh_holes failed rc={rc}: "
+                    f"{err.decode() if err else 'unknown'}")
+            return result, self._collect(out, True)
+
+    def _collect(self, out, copy: bool) -> dict:
+        """Meshset descriptor -> {label: (verts, faces)}; frees it."""
+        result = {}
+        try:
+            ms = out.contents
+            n = int(ms.nmeshes)
+            if n:
+                # one GIL-releasing memmove per flat buffer (the flat
+                # buffers are ctx-owned pinned staging, valid until
+                # the next call on this ctx), then per-label views
+                tv, tt = int(ms.total_verts), int(ms.total_tris)
+                if copy:
+                    all_v = np.empty((tv, 3), dtype=np.float32)
+                    all_f = np.empty((tt, 3), dtype=np.uint32)
+                    if tv:
+                        ctypes.memmove(all_v.ctypes.data, ms.verts_base,
+                                       tv * 12)
+                    if tt:
+                        ctypes.memmove(all_f.ctypes.data, ms.faces_base,
+                                       tt * 12)
+                else:
+                    all_v = np.ctypeslib.as_array(
+                        ms.verts_base, shape=(max(tv, 1), 3))[:tv]
+                    all_f = np.ctypeslib.as_array(
+                        ms.faces_base, shape=(max(tt, 1), 3))[:tt]
+                labels = np.ctypeslib.as_array(
+                    ms.labels_arr, shape=(n,)).tolist()
+                voff = np.ctypeslib.as_array(
+                    ms.voff_arr, shape=(n,)).tolist()
+                nv = np.ctypeslib.as_array(
+                    ms.nv_arr, shape=(n,)).tolist()
+                foff = np.ctypeslib.as_array(
+                    ms.foff_arr, shape=(n,)).tolist()
+                nf = np.ctypeslib.as_array(
+                    ms.nf_arr, shape=(n,)).tolist()
+                result = {
+                    lab: (all_v[vo:vo + kv], all_f[fo:fo + kf])
+                    for lab, vo, kv, fo, kf
+                    in zip(labels, voff, nv, foff, nf)
+                }
+        finally:
+            self.lib.mg_meshset_free(out)
         return result
+
+    def fill_holes(self, labels: np.ndarray, level: int = 1):
+        """Hole filling of one F-order uint32/uint64 volume on the GPU
+        (mg_fill_holes; the fastmorph.fill_holes_v2 replacement of
+        mesh.py:220 for levels 1-2, contract in DESIGN.md §7).
+        -> (filled, holes, rounds): the filled volume, the hole volume
+        (labels[v] where filled[v] != labels[v], else 0) and the number
+        of productive 3-D rounds."""
+        level = int(level)
+        if level not in (1, 2):
+            raise NotImplementedError(
+                f"fill_holes level {level}: the engine implements levels "
+                f"1-2; level 3 needs a multilabel dilation and levels >= 4 "
+                f"a merge threshold")
+        labels = np.asfortranarray(labels)
+        if labels.dtype == np.uint32:
+            dtype = MG_U32
+        elif labels.dtype == np.uint64:
+            dtype = MG_U64
+        else:
+            raise ValueError(f"unsupported label dtype {labels.dtype}")
+        if labels.ndim != 3:
+            raise ValueError("fill_holes expects a 3-D volume")
+        sx, sy, sz = labels.shape
+        filled = np.empty(labels.shape, dtype=labels.dtype, order="F")
+        holes = np.empty(labels.shape, dtype=labels.dtype, order="F")
+        rounds = ctypes.c_uint32()
+        with self._lock:
+            rc = self.lib.mg_fill_holes(
+                self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
+                sx, sy, sz, dtype, level,
+                filled.ctypes.data_as(ctypes.c_void_p),
+                holes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rounds))
+            if rc != 0:
+                err = self.lib.mg_last_error(self.ctx)
+                raise RuntimeError(
+                    f"mg_fill_holes failed rc={rc}: "
+                    f"{err.decode() if err else 'unknown'}")
+        return filled, holes, int(rounds.value)
 
     def simplify_mesh(self, verts: np.ndarray, faces: np.ndarray,
                       reduction_factor: int,
@@ -327,7 +445,7 @@ class Engine:
         return out_v, out_f
 
     def stats(self) -> dict:
-        s = MgStats()
+        s = MgStatsFill()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
         if rc != 0:
             raise RuntimeError("mg_get_stats failed")
@@ -338,14 +456,16 @@ def mesh_chunk(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                reduction_factor: int = 0, max_error: float = 40.0,
                voxel_centered: bool = True, device_id: Optional[int] = None,
                dust_threshold: int = 0,
-               copy: bool = True, label_map=None) -> dict:
-    """Module-level product mesher (the default MeshTask path)."""
+               copy: bool = True, label_map=None, fill_holes: int = 0):
+    """Module-level product mesher (the default MeshTask path). With
+    fill_holes=1|2 returns the pair (filled_meshes, hole_meshes)."""
     if device_id is None:
         device_id = int(os.environ.get("MESHGINE_DEVICE",
                                        os.environ.get("LOCAL_RANK", "0")))
     return Engine.get(device_id).mesh_chunk(
         labels, resolution, reduction_factor, max_error, voxel_centered,
-        dust_threshold=dust_threshold, copy=copy, label_map=label_map)
+        dust_threshold=dust_threshold, copy=copy, label_map=label_map,
+        fill_holes=fill_holes)
 
 
 # MeshTask checks this to delegate dust_threshold preprocessing to the
@@ -355,6 +475,19 @@ mesh_chunk.handles_dust = True
 # into one label_map (remap.fold_label_ops) instead of the host numpy
 # mask_except/remap/mask sequence
 mesh_chunk.handles_label_map = True
+# ... and fill_holes levels 1-2 (device volume pass after dust and the
+# label map; the call then returns (filled_meshes, hole_meshes))
+mesh_chunk.handles_fill_holes = True
+
+
+def fill_holes(labels: np.ndarray, level: int = 1,
+               device_id: Optional[int] = None):
+    """Module-level hole filling -> (filled, holes, rounds); see
+    Engine.fill_holes."""
+    if device_id is None:
+        device_id = int(os.environ.get("MESHGINE_DEVICE",
+                                       os.environ.get("LOCAL_RANK", "0")))
+    return Engine.get(device_id).fill_holes(labels, level)
 
 
 def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,

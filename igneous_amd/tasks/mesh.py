@@ -18,7 +18,10 @@ HIP engine produces all labels' welded (and optionally simplified) meshes.
 dust_threshold and the label selection (remap_table / object_ids /
 exclude_object_ids, folded by remap.fold_label_ops) ride the same call as
 device volume passes when the mesher advertises handles_dust /
-handles_label_map.
+handles_label_map. fill_holes levels 1-2 (mesh.py:211-243) ride it too when
+the mesher advertises handles_fill_holes: the fill runs on the device after
+dust and the label selection, the call returns the filled volume's meshes
+and the hole volume's meshes, and the two are concatenated per segment id.
 There is no CPU fallback; a missing engine raises.
 
 Deliberate deviations (documented in DESIGN.md):
@@ -27,8 +30,10 @@ Deliberate deviations (documented in DESIGN.md):
   - dry_run returns (meshes, bounding_boxes) computed; the reference's
     dry_run references bounding_boxes before assignment (mesh.py:249-252,
     a latent NameError).
-  - fill_holes>0 and dust_global raise NotImplementedError (out of the
-    hot-path scope). Sharded output uses the in-repo
+  - fill_holes 1-2 follow this repository's own written contract
+    (DESIGN.md §7; fastmorph's source is not available to pin against);
+    fill_holes>=3 (multilabel dilation, merge threshold) and dust_global
+    raise NotImplementedError. Sharded output uses the in-repo
     MapBuffer restatement and draco encoding the in-repo Draco
     restatement (formats/, byte-level external parity unpinned offline
     — DESIGN.md §7).
@@ -131,10 +136,19 @@ class MeshTask(RegisteredTask):
     # ------------------------------------------------------------------
     def execute(self):
         opts = self.options
-        if opts['fill_holes'] > 0:
+        fill_level = int(opts['fill_holes'] or 0)
+        if fill_level >= 3:
             raise NotImplementedError(
-                "fill_holes>0 requires fastmorph/crackle (out of scope, "
-                "SURVEY §2 'fastmorph, crackle' row)")
+                "fill_holes>=3 is not implemented: level 3 needs "
+                "fastmorph's multilabel dilation and levels >= 4 its "
+                "merge_threshold, whose tie rules cannot be restated "
+                "without the fastmorph source (DESIGN.md §7)")
+        if fill_level > 0 and not getattr(
+                _get_mesher(), 'handles_fill_holes', False):
+            raise NotImplementedError(
+                "fill_holes>0 needs a mesher that fills holes itself "
+                "(handles_fill_holes): the HIP engine does, the injected "
+                "mesher does not")
 
         self._volume = PrecomputedVolume(
             self.layer_path, opts['mip'], bounded=False,
@@ -232,6 +246,10 @@ class MeshTask(RegisteredTask):
             extra['dust_threshold'] = device_dust
         if label_map is not None:
             extra['label_map'] = label_map
+        if fill_level:
+            # after dust and the label handling above, host or device
+            # (mesh.py:193-228); the mesher returns (filled, holes)
+            extra['fill_holes'] = fill_level
         try:
             raw = mesher(
                 data,
@@ -252,10 +270,23 @@ class MeshTask(RegisteredTask):
                 **extra,
             )
         del data
+        hole_raw = {}
+        if fill_level:
+            raw, hole_raw = raw
         meshes = {
             int(label): Mesh(verts, faces, id=int(label))
             for label, (verts, faces) in raw.items()
         }
+        # mesh.py:238-242: a segment's hole mesh is appended to its filled
+        # mesh; a segment present only in the hole volume keeps that alone
+        for label, (verts, faces) in hole_raw.items():
+            segid = int(label)
+            hole_mesh = Mesh(verts, faces, id=segid)
+            if segid in meshes:
+                meshes[segid] = Mesh.concatenate(
+                    meshes[segid], hole_mesh, id=segid)
+            else:
+                meshes[segid] = hole_mesh
 
         bounding_boxes = {}
         binaries = {}

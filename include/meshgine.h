@@ -27,6 +27,16 @@
  *                        (mesh.py:200-204: mask_except, mask). The three
  *                        fold into one {key -> val} table + a miss policy
  *                        (mg_label_map) applied in one device volume pass.
+ *   mg_fill_holes      — replaces fastmorph.fill_holes_v2 (mesh.py:220) for
+ *                        fill_holes levels 1-2: host volume in, filled and
+ *                        hole volumes out, computed as device volume passes
+ *                        (contract: DESIGN.md §7).
+ *   mg_mesh_chunk_filled — mg_mesh_chunk_mapped plus that fill between the
+ *                        label map and the mesher (mesh.py:211-230); the
+ *                        hole volume stays on the device.
+ *   mg_mesh_holes      — replaces the second Mesher.mesh(hole_labels) +
+ *                        compute_meshes (mesh.py:234-235) on the hole
+ *                        volume left resident by mg_mesh_chunk_filled.
  *   mg_meshset_free    — replaces Python GC of zmesh.Mesh objects.
  *   mg_last_error      — error text for the last failed call on this ctx.
  *
@@ -125,6 +135,9 @@ typedef struct {
   double ms_labelmap;   /* label map: table upload + build + volume pass,
                            after H2D/dust and before pass 1 (0 if no map;
                            also inside ms_total) */
+  double ms_fill;       /* fill_holes: label ids + rounds + hole volume,
+                           after the label map and before pass 1 (0 without
+                           fill; also inside ms_total) */
 } mg_stats;
 
 /* Label selection folded into one lookup table (replaces the host
@@ -190,6 +203,51 @@ int mg_mesh_chunk_mapped(mg_ctx *ctx, const void *labels,
                          uint32_t flags,
                          const mg_label_map *map,
                          mg_meshset **out);
+
+/* mg_mesh_chunk_mapped with hole filling (fill_level 0 = none, identical
+ * to mg_mesh_chunk_mapped). Replaces fastmorph.fill_holes_v2 + the mesher
+ * call on filled_labels (mesh.py:220-232). Device order: H2D -> dust ->
+ * label map -> fill -> count/emit/.../extract on the FILLED volume. The
+ * hole volume (input label where the fill changed it, else 0) stays
+ * resident on the ctx for one mg_mesh_holes call.
+ * fill_level 1: rounds to a fixed point; 2: the six boundary slices are
+ * filled in 2-D first (fix_borders). Errors: fill_level > 2, or
+ * fill_level > 0 combined with MG_FLAG_SKIP_H2D. */
+int mg_mesh_chunk_filled(mg_ctx *ctx, const void *labels,
+                         int sx, int sy, int sz, int dtype,
+                         float rx, float ry, float rz,
+                         uint32_t reduction_factor, float max_error,
+                         int voxel_centered, uint64_t dust_threshold,
+                         uint32_t flags,
+                         const mg_label_map *map,
+                         uint32_t fill_level,
+                         mg_meshset **out);
+
+/* Mesh the hole volume left by the last mg_mesh_chunk_filled
+ * (fill_level > 0) on this ctx — replaces Mesher.mesh(hole_labels) +
+ * compute_meshes at mesh.py:234-235. The volume is already resident: no
+ * upload. Consumes the stash (the hole volume becomes the ctx's resident
+ * label volume); a call without a stash is an error, and any other
+ * mg_mesh_chunk* / mg_fill_holes call on the ctx drops it. flags: only
+ * MG_FLAG_DEVICE_ONLY is honoured. The result reuses the ctx's staging
+ * like any mg_mesh_chunk: copy the filled meshset first. */
+int mg_mesh_holes(mg_ctx *ctx, float rx, float ry, float rz,
+                  uint32_t reduction_factor, float max_error,
+                  int voxel_centered, uint32_t flags,
+                  mg_meshset **out);
+
+/* Standalone hole filling of a host volume — replaces
+ * fastmorph.fill_holes_v2 at mesh.py:220 (levels 1-2 only).
+ *   labels       host, sx*sy*sz elements, F-order
+ *   level        1 | 2 (anything else is an error)
+ *   filled_out   caller buffer, same size/dtype: the filled volume
+ *   holes_out    caller buffer: labels[v] where filled[v] != labels[v]
+ *   rounds_out   optional: productive 3-D rounds (rounds that rewrote)
+ * More than 63 productive rounds on one block is a "did not converge"
+ * error. Drops any stashed hole volume. Returns 0 on success. */
+int mg_fill_holes(mg_ctx *ctx, const void *labels,
+                  int sx, int sy, int sz, int dtype, uint32_t level,
+                  void *filled_out, void *holes_out, uint32_t *rounds_out);
 
 void mg_meshset_free(mg_meshset *ms);
 

@@ -282,45 +282,19 @@ static int run_fill_holes(mg_ctx *c, int dtype, int sx, int sy, int sz,
     HIP_TRY(c, hipMemcpyAsync(vol, c->labels.ptr, nvox * 4,
                               hipMemcpyDeviceToDevice, s), 51);
   } else {
-    for (;;) {  // label hash, grow-and-retry like the dust passes
-      if (ensure(c, c->lh_keys, c->lh_slots * 8)) return 51;
-      if (ensure(c, c->lh_vals, c->lh_slots * 4)) return 51;
-      if (ensure(c, c->lh_misc, 256)) return 51;
-      HIP_TRY(c, hipMemsetAsync(c->lh_keys.ptr, 0, c->lh_slots * 8, s), 51);
-      HIP_TRY(c, hipMemsetAsync(c->lh_misc.ptr, 0, 256, s), 51);
-      LabelHash lh;
-      lh.keys = (uint64_t *)c->lh_keys.ptr;
-      lh.vals = (uint32_t *)c->lh_vals.ptr;
-      lh.counter = (uint32_t *)c->lh_misc.ptr;
-      lh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
-      lh.nslots = c->lh_slots;
-      hipLaunchKernelGGL(k_dust_build<uint64_t>, dim3(4096), dim3(256), 0, s,
-                         (const uint64_t *)c->labels.ptr, nvox, lh);
-      uint32_t misc[2] = {0, 0};
-      HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8,
-                                hipMemcpyDeviceToHost, s), 51);
-      HIP_TRY(c, hipStreamSynchronize(s), 51);
-      if (misc[1]) {
-        if (c->lh_slots >= (1ull << 27)) {
-          SET_ERR(c, "label hash overflow (fill_holes) at %llu slots",
-                  (unsigned long long)c->lh_slots);
-          return 51;
-        }
-        c->lh_slots <<= 2;
-        continue;
-      }
-      const uint32_t nl = misc[0];
-      if (ensure(c, c->label_values, (uint64_t)std::max(nl, 1u) * 8))
-        return 51;
-      hipLaunchKernelGGL(k_label_values,
-                         dim3((uint32_t)((c->lh_slots + 255) / 256)),
-                         dim3(256), 0, s, lh,
-                         (uint64_t *)c->label_values.ptr, c->lh_slots);
-      hipLaunchKernelGGL(k_fill_to_ids, vnb, blk, 0, s,
-                         (const uint64_t *)c->labels.ptr, nvox, lh, vol);
-      HIP_TRY(c, hipGetLastError(), 51);
-      break;
-    }
+    uint32_t nl = 0;  // label hash, grow-and-retry like the dust passes
+    if (int e = hash_volume_labels(c, dtype, nvox, " (fill_holes)", 51, &nl))
+      return e;
+    const LabelHash lh = label_hash_view(c);
+    if (ensure(c, c->label_values, (uint64_t)std::max(nl, 1u) * 8))
+      return 51;
+    hipLaunchKernelGGL(k_label_values,
+                       dim3((uint32_t)((c->lh_slots + 255) / 256)),
+                       dim3(256), 0, s, lh,
+                       (uint64_t *)c->label_values.ptr, c->lh_slots);
+    hipLaunchKernelGGL(k_fill_to_ids, vnb, blk, 0, s,
+                       (const uint64_t *)c->labels.ptr, nvox, lh, vol);
+    HIP_TRY(c, hipGetLastError(), 51);
   }
 
   const uint64_t usx = sx, usy = sy, usz = sz, sxy = usx * usy;
@@ -351,15 +325,15 @@ static int run_fill_holes(mg_ctx *c, int dtype, int sx, int sy, int sz,
   int rc = fill_run_rounds(c, full, "the volume", rounds_out);
   if (rc) return rc;
 
-  if (dtype == MG_U64)
-    hipLaunchKernelGGL(k_fill_finish<uint64_t>, vnb, blk, 0, s,
-                       (uint64_t *)c->labels.ptr, (uint64_t *)c->holes.ptr,
-                       (const uint32_t *)vol,
-                       (const uint64_t *)c->label_values.ptr, nvox);
-  else
-    hipLaunchKernelGGL(k_fill_finish<uint32_t>, vnb, blk, 0, s,
-                       (uint32_t *)c->labels.ptr, (uint32_t *)c->holes.ptr,
-                       (const uint32_t *)vol, (const uint64_t *)nullptr, nvox);
+  // ids back to values through label_values (u64 only: u32 ids ARE labels)
+  const uint64_t *values =
+      dtype == MG_U64 ? (const uint64_t *)c->label_values.ptr : nullptr;
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_fill_finish<T>, vnb, blk, 0, s, (T *)c->labels.ptr,
+                       (T *)c->holes.ptr, (const uint32_t *)vol, values,
+                       nvox);
+  });
   HIP_TRY(c, hipGetLastError(), 54);
   return 0;
 }

@@ -780,24 +780,43 @@ __global__ void k_any_active(const uint8_t *active, uint32_t nlabels,
 // ---------------------------------------------------------------------------
 // context / host side
 
-struct DevBuf {
+// Move-only owner of one hipMalloc'd (DevBuf) or pinned (HostBuf) block.
+// Moving nulls the source, so std::swap(c->faces, c->simp_faces_alt)
+// exchanges the blocks without a free in the swap's temporary.
+template <hipError_t (*FREE)(void *)>
+struct OwnedBuf {
   void *ptr = nullptr;
   size_t cap = 0;
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf &) = delete;
+  OwnedBuf &operator=(const OwnedBuf &) = delete;
+  OwnedBuf(OwnedBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) {
+    o.ptr = nullptr;
+    o.cap = 0;
+  }
+  OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      ptr = o.ptr;
+      cap = o.cap;
+      o.ptr = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
+  ~OwnedBuf() { release(); }
+  void release() {
+    if (ptr) (void)FREE(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
 };
+using DevBuf = OwnedBuf<hipFree>;
+using HostBuf = OwnedBuf<hipHostFree>;
 
-struct HostBuf {
-  void *ptr = nullptr;
-  size_t cap = 0;
-};
-
-struct mg_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // concurrent simplify band
-  std::mutex lock;
-  std::string err;
-  mg_stats stats = {};
-  // device buffers (grow-only cache)
+// Every device buffer of a context (grow-only cache). This is the one
+// list: ~mg_ctx releases the struct as a whole.
+struct DeviceBuffers {
   DevBuf labels, segcnt, segoff, scan_tmp,
       lh_keys, lh_vals, lh_misc,
       tri_label, tri_label_alt, order, order_alt, tri_keys, keys_sorted,
@@ -808,18 +827,62 @@ struct mg_ctx {
       simp_Q, simp_pick, simp_remap, simp_flab, simp_flab_alt,
       simp_faces_alt, simp_verts_alt, simp_vbase_alt, simp_meta, simp_ref,
       simp_keep, simp_keep_scan, simp_park, simp_first, simp_troff_final,
-      simp_deg, simp_adj, simp_rh, simp_sched, simp_accept,
+      simp_deg, simp_adj, simp_rh, simp_accept,
       map_tab, map_keys, map_vals,  // label map table + staged pairs
       // fill_holes: u32 working volume, union-find parents, per-root
       // neighbour min/max, rewrite counter, resident hole volume
       fill_vol, fill_parent, fill_cmin, fill_cmax, fill_misc, holes;
+};
+
+// Timing / ordering events of one mesh_chunk_impl call. EV_H2D_END is
+// recorded TWICE: after the upload, and again at the start of the count
+// pass — so ms_h2d (EV_START..EV_H2D_END) spans upload + dust + label map
+// + fill, and ms_count starts where it ends. Benchmarks and the stored
+// profiles were taken with that meaning; keep it.
+enum {
+  EV_START = 0,
+  EV_H2D_END,
+  EV_COUNT_END,
+  EV_SCAN_END,
+  EV_EMIT_END,
+  EV_PARTITION_END,
+  EV_WELD_END,
+  EV_END,           // after the extract
+  EV_SIMPLIFY_END,
+  EV_SIMP_FORK,     // stream2 waits for the simplify setup
+  EV_SIMP_JOIN,     // stream waits for stream2's bands
+  EV_MAP_START,
+  EV_MAP_END,
+  EV_FILL_START,
+  EV_FILL_END,
+  EV_COUNT_
+};
+
+struct mg_ctx : DeviceBuffers {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr;  // concurrent simplify band
+  std::mutex lock;
+  std::string err;
+  mg_stats stats = {};
   // hole volume stashed by the last mg_mesh_chunk_filled (mg_mesh_holes
   // consumes it)
   bool holes_valid = false;
   int holes_sx = 0, holes_sy = 0, holes_sz = 0, holes_dtype = 0;
   uint64_t lh_slots = 1ull << 20;
   HostBuf h_verts, h_faces;  // pinned output staging, reused across calls
-  hipEvent_t ev[16] = {};
+  hipEvent_t ev[EV_COUNT_] = {};
+
+  // release order: device buffers, pinned buffers, events, stream2, stream
+  ~mg_ctx() {
+    (void)hipSetDevice(device);
+    static_cast<DeviceBuffers &>(*this) = DeviceBuffers();  // frees each
+    h_verts.release();
+    h_faces.release();
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    if (stream2) (void)hipStreamDestroy(stream2);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 static thread_local std::string g_err;  // for ctx==NULL failures
@@ -843,9 +906,7 @@ static thread_local std::string g_err;  // for ctx==NULL failures
 
 static int ensure_host(mg_ctx *c, HostBuf &b, size_t bytes) {
   if (b.cap >= bytes) return 0;
-  if (b.ptr) (void)hipHostFree(b.ptr);
-  b.ptr = nullptr;
-  b.cap = 0;
+  b.release();
   size_t want = bytes + bytes / 4;
   if (hipHostMalloc(&b.ptr, want) != hipSuccess) {
     if (hipHostMalloc(&b.ptr, bytes) != hipSuccess) {
@@ -861,9 +922,7 @@ static int ensure_host(mg_ctx *c, HostBuf &b, size_t bytes) {
 
 static int ensure(mg_ctx *c, DevBuf &b, size_t bytes) {
   if (b.cap >= bytes) return 0;
-  if (b.ptr) (void)hipFree(b.ptr);
-  b.ptr = nullptr;
-  b.cap = 0;
+  b.release();
   size_t want = bytes + bytes / 4;  // 25% headroom to damp re-allocs
   hipError_t e = hipMalloc(&b.ptr, want);
   if (e != hipSuccess) {
@@ -877,6 +936,125 @@ static int ensure(mg_ctx *c, DevBuf &b, size_t bytes) {
   }
   b.cap = want;
   return 0;
+}
+
+// Call f with a zero of the volume's label type, f(uint32_t{}) or
+// f(uint64_t{}), so a templated launch is written once:
+//   by_dtype(dtype, [&](auto t) { using T = decltype(t); ...k_x<T>... });
+template <typename F>
+static auto by_dtype(int dtype, F &&f) {
+  if (dtype == MG_U64) return f(uint64_t{});
+  return f(uint32_t{});
+}
+
+// rocPRIM's two-call pattern: size query, grow the temp buffer, run.
+// call(tmp_ptr, tmp_bytes) wraps the primitive; the two texts and rc are
+// the caller's error for a failed size query / a failed run.
+template <typename F>
+static int rocprim_two_call(mg_ctx *c, DevBuf &tmp, const char *err_size,
+                            const char *err_run, int rc, F call) {
+  size_t bytes = 0;
+  if (call(nullptr, bytes) != hipSuccess) {
+    SET_ERR(c, "%s", err_size);
+    return rc;
+  }
+  if (ensure(c, tmp, bytes)) return rc;
+  if (call(tmp.ptr, bytes) != hipSuccess) {
+    SET_ERR(c, "%s", err_run);
+    return rc;
+  }
+  return 0;
+}
+
+// Exclusive plus-scan of n u32 values from `in` into `out` on stream s,
+// temp storage in c->scan_tmp. In is a template parameter only so that
+// each call site keeps the iterator type it always instantiated rocPRIM
+// with (uint32_t *, or the weld's popcount transform iterator).
+template <typename In>
+static int scan_u32(mg_ctx *c, In in, uint32_t *out, size_t n, hipStream_t s,
+                    const char *err_size, const char *err_run, int rc) {
+  return rocprim_two_call(
+      c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n,
+                                       rocprim::plus<uint32_t>(), s);
+      });
+}
+
+// Stable radix sort of n (u32 key, V value) pairs on bits [begin, end) on
+// stream s, temp storage in c->sort_tmp; results in the buffers' current().
+template <typename V>
+static int sort_pairs(mg_ctx *c, rocprim::double_buffer<uint32_t> &keys,
+                      rocprim::double_buffer<V> &vals, size_t n,
+                      unsigned begin_bit, unsigned end_bit, hipStream_t s,
+                      const char *err_size, const char *err_run, int rc) {
+  return rocprim_two_call(
+      c, c->sort_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keys, vals, n,
+                                         begin_bit, end_bit, s);
+      });
+}
+
+// ---------------------------------------------------------------------------
+// label hash, host side: lh_keys/lh_vals hold c->lh_slots slots; lh_misc
+// word 0 is the id counter, word 1 the overflow flag (words 2.. are
+// scratch scalars of later stages).
+
+static LabelHash label_hash_view(mg_ctx *c) {
+  LabelHash lh;
+  lh.keys = (uint64_t *)c->lh_keys.ptr;
+  lh.vals = (uint32_t *)c->lh_vals.ptr;
+  lh.counter = (uint32_t *)c->lh_misc.ptr;
+  lh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
+  lh.nslots = c->lh_slots;
+  return lh;
+}
+
+// size the hash for c->lh_slots and clear it
+static int label_hash_reset(mg_ctx *c, int rc) {
+  if (ensure(c, c->lh_keys, c->lh_slots * 8)) return rc;
+  if (ensure(c, c->lh_vals, c->lh_slots * 4)) return rc;
+  if (ensure(c, c->lh_misc, 256)) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->lh_keys.ptr, 0, c->lh_slots * 8, c->stream),
+          rc);
+  HIP_TRY(c, hipMemsetAsync(c->lh_misc.ptr, 0, 256, c->stream), rc);
+  return 0;
+}
+
+// the build overflowed: grow x4 for the retry, or fail at 2^27 slots.
+// `where` ("", " (dust)", " (fill_holes)") names the pass in the error.
+static int label_hash_grow(mg_ctx *c, const char *where, int rc) {
+  if (c->lh_slots >= (1ull << 27)) {
+    SET_ERR(c, "label hash overflow%s at %llu slots", where,
+            (unsigned long long)c->lh_slots);
+    return rc;
+  }
+  c->lh_slots <<= 2;
+  return 0;
+}
+
+// Hash every non-zero label of the resident volume (dust and the u64
+// fill path), growing until it fits. *p_n = distinct labels.
+static int hash_volume_labels(mg_ctx *c, int dtype, uint64_t nvox,
+                              const char *where, int rc, uint32_t *p_n) {
+  hipStream_t s = c->stream;
+  for (;;) {
+    if (int e = label_hash_reset(c, rc)) return e;
+    const LabelHash lh = label_hash_view(c);
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_dust_build<T>, dim3(4096), dim3(256), 0, s,
+                         (const T *)c->labels.ptr, nvox, lh);
+    });
+    uint32_t misc[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8, hipMemcpyDeviceToHost,
+                              s), rc);
+    HIP_TRY(c, hipStreamSynchronize(s), rc);
+    if (!misc[1]) {
+      *p_n = misc[0];
+      return 0;
+    }
+    if (int e = label_hash_grow(c, where, rc)) return e;
+  }
 }
 
 #include "fill_holes.hip"
@@ -899,50 +1077,20 @@ mg_ctx *mg_init(int device_id) {
   if (hipSetDevice(device_id) != hipSuccess) return nullptr;
   mg_ctx *c = new mg_ctx();
   c->device = device_id;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) !=
-      hipSuccess) {
-    delete c;
+  bool ok =
+      hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) ==
+          hipSuccess &&
+      hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) ==
+          hipSuccess;
+  for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!ok) {
+    delete c;  // ~mg_ctx destroys whatever was created
     return nullptr;
   }
-  if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) !=
-      hipSuccess) {
-    delete c;
-    return nullptr;
-  }
-  for (auto &e : c->ev)
-    if (hipEventCreate(&e) != hipSuccess) { delete c; return nullptr; }
   return c;
 }
 
-void mg_destroy(mg_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  for (auto *b : {&c->labels, &c->segcnt, &c->segoff, &c->scan_tmp,
-                  &c->lh_keys, &c->lh_vals, &c->lh_misc, &c->tri_label,
-                  &c->tri_label_alt, &c->order, &c->order_alt, &c->tri_keys,
-                  &c->keys_sorted, &c->tri_off, &c->sort_tmp, &c->wh_keys,
-                  &c->vtx_scan,
-                  &c->verts, &c->faces, &c->vbase, &c->label_values,
-                  &c->simp_fq, &c->simp_valid, &c->simp_pk, &c->simp_pk_alt,
-                  &c->simp_pv, &c->simp_pv_alt, &c->simp_Q, &c->simp_pick,
-                  &c->simp_remap, &c->simp_flab, &c->simp_flab_alt,
-                  &c->simp_faces_alt, &c->simp_verts_alt, &c->simp_vbase_alt,
-                  &c->simp_meta, &c->simp_ref, &c->simp_keep,
-                  &c->simp_keep_scan, &c->simp_park, &c->simp_first,
-                  &c->simp_troff_final, &c->simp_deg, &c->simp_adj,
-                  &c->simp_rh, &c->simp_sched, &c->simp_accept,
-                  &c->map_tab, &c->map_keys, &c->map_vals,
-                  &c->fill_vol, &c->fill_parent, &c->fill_cmin,
-                  &c->fill_cmax, &c->fill_misc, &c->holes}) {
-    if (b->ptr) (void)hipFree(b->ptr);
-  }
-  if (c->h_verts.ptr) (void)hipHostFree(c->h_verts.ptr);
-  if (c->h_faces.ptr) (void)hipHostFree(c->h_faces.ptr);
-  for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void mg_destroy(mg_ctx *c) { delete c; }
 
 const char *mg_last_error(mg_ctx *c) {
   return c ? c->err.c_str() : g_err.c_str();
@@ -960,18 +1108,1023 @@ void mg_meshset_free(mg_meshset *ms) {
   free(ms);
 }
 
+}  // extern "C"
+
+// a meshset with no meshes (the caller frees it like any other)
+static mg_meshset *empty_meshset() {
+  return (mg_meshset *)calloc(1, sizeof(mg_meshset) + 2 * sizeof(void *));
+}
+
+static double ev_ms(mg_ctx *c, int a, int b) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->ev[a], c->ev[b]) != hipSuccess) return 0.0;
+  return (double)ms;
+}
+
 // ---------------------------------------------------------------------------
+// GPU quadric simplification driver (kernels in simplify.hip); mirrors
+// oracle/simplify.c round for round.
+
+#define SIMP_BLK 256
+// labels up to SIMP_BIG_CAP faces simplify entirely inside one workgroup
+// each (cache-resident round loop, no global sorts); only bigger labels
+// go through the global-rounds machinery.
+#define SIMP_BIG_CAP 65536u
+
+static inline uint32_t simp_blocks(uint64_t n) {
+  return (uint32_t)((n + SIMP_BLK - 1) / SIMP_BLK);
+}
+
+// Environment switches of the simplifier, read once per call.
+struct SimpEnv {
+  uint32_t propose;  // MG_SIMP_PROPOSE=0 disables the proposal-acceptance
+                     // second matching wave (contract knob shared with
+                     // the oracle, which reads the same variable)
+  uint32_t subs;     // MG_SIMP_SUBS: sub-rounds per quadric recompute in
+                     // the per-label kernel (contract constant, default 6
+                     // on both sides)
+  bool prof;         // MG_SIMP_PROF: per-phase cycle counters to stderr
+  bool roundhist;    // MG_SIMP_ROUNDHIST: round-count histograms to stderr
+};
+
+static SimpEnv read_simp_env() {
+  SimpEnv env = {1u, 6u, false, false};
+  const char *e = getenv("MG_SIMP_PROPOSE");
+  if (e && e[0] == '0') env.propose = 0;
+  e = getenv("MG_SIMP_SUBS");
+  if (e && e[0]) { int v = atoi(e); env.subs = v < 1 ? 1u : (uint32_t)v; }
+  env.prof = getenv("MG_SIMP_PROF") != nullptr;
+  env.roundhist = getenv("MG_SIMP_ROUNDHIST") != nullptr;
+  return env;
+}
+
+// Per-call values of one run_simplify.
+struct SimpCall {
+  SimpEnv env;
+  uint64_t L, V;     // labels, vertices (V is fixed until the final compact)
+  float max_cost;
+  // c->simp_meta: [0,L) nt_cur | [L,2L) target | [2L,3L) nt_new |
+  //               3L..: active u8[L] | any u32 (aligned)
+  uint32_t *nt_cur, *target, *nt_new;
+  uint8_t *active;
+  uint32_t *d_any;
+  unsigned long long *d_prof;  // 6 phase counters, or null
+  uint32_t *d_rh;              // round histogram (176 u32), or null
+};
+
+static int simp_alloc(mg_ctx *c, SimpCall &k, uint64_t T) {
+  const uint64_t L = k.L, V = k.V;
+  const uint64_t meta_bytes = L * 12 + ((L + 3) & ~3ull) + 4;
+  if (ensure(c, c->simp_meta, meta_bytes)) return 40;
+  k.nt_cur = (uint32_t *)c->simp_meta.ptr;
+  k.target = k.nt_cur + L;
+  k.nt_new = k.target + L;
+  k.active = (uint8_t *)(k.nt_new + L);
+  k.d_any = (uint32_t *)((char *)c->simp_meta.ptr +
+                         L * 12 + ((L + 3) & ~3ull));
+  if (ensure(c, c->simp_flab, T * 4)) return 40;
+  if (ensure(c, c->simp_flab_alt, T * 4)) return 40;
+  if (ensure(c, c->simp_faces_alt, T * 12)) return 40;
+  if (ensure(c, c->simp_fq, T * sizeof(SimpPlane))) return 40;
+  if (ensure(c, c->simp_valid, T)) return 40;
+  if (ensure(c, c->simp_pk, 3 * T * 4)) return 40;
+  if (ensure(c, c->simp_pk_alt, 3 * T * 4)) return 40;
+  if (ensure(c, c->simp_pv, 3 * T * 4)) return 40;
+  if (ensure(c, c->simp_pv_alt, 3 * T * 4)) return 40;
+  if (ensure(c, c->simp_Q, V * 48)) return 40;  // 12-float rows
+  if (ensure(c, c->simp_pick, V * 8)) return 40;
+  if (ensure(c, c->simp_remap, V * 4)) return 40;
+  if (ensure(c, c->simp_keep, T * 4)) return 40;
+  if (ensure(c, c->simp_keep_scan, T * 4)) return 40;
+  if (ensure(c, c->simp_park, 3 * T * 4)) return 40;
+  if (ensure(c, c->simp_first, (L + 1) * 4)) return 40;
+  if (ensure(c, c->simp_troff_final, (L + 1) * 4)) return 40;
+  if (ensure(c, c->simp_deg, V * 4)) return 40;
+  if (ensure(c, c->simp_adj, V * 4)) return 40;
+  if (ensure(c, c->simp_accept, V * 4)) return 40;
+  return 0;
+}
+
+// MG_SIMP_PROF / MG_SIMP_ROUNDHIST printouts of the per-label launch
+static int simp_print_diagnostics(mg_ctx *c, const SimpCall &k) {
+  hipStream_t s = c->stream;
+  if (k.d_prof) {
+    unsigned long long hp[6];
+    HIP_TRY(c, hipMemcpyAsync(hp, k.d_prof, 48, hipMemcpyDeviceToHost, s),
+            40);
+    HIP_TRY(c, hipStreamSynchronize(s), 40);
+    const char *nm[6] = {"loophead", "planes+deg", "scan+fill",
+                         "sortaccum", "picks", "collapse+compact"};
+    fprintf(stderr, "[mg simp phases, summed tid0 cycles]");
+    for (int i = 0; i < 6; ++i) fprintf(stderr, " %s=%llu", nm[i], hp[i]);
+    fprintf(stderr, "\n");
+  }
+  if (k.d_rh) {
+    uint32_t h[176];
+    HIP_TRY(c, hipMemcpyAsync(h, k.d_rh, 176 * 4, hipMemcpyDeviceToHost, s),
+            40);
+    HIP_TRY(c, hipStreamSynchronize(s), 40);
+    fprintf(stderr, "[mg simp rounds] labels=%u sum_groups=%u "
+            "sum_subs=%u sum_nt0=%u max_cycles=%u (nt0=%u)\n",
+            h[130], h[128], h[129], h[131], h[132], h[133]);
+    unsigned long long lds_c, glob_c;
+    memcpy(&lds_c, &h[160], 8);
+    memcpy(&glob_c, &h[162], 8);
+    fprintf(stderr, "[mg simp mode split] lds: n=%u cyc=%llu | "
+            "global: n=%u cyc=%llu\n", h[164], lds_c, h[165], glob_c);
+    fprintf(stderr, "[mg simp log2-cycle hist]");
+    for (int i = 0; i < 26; ++i)
+      if (h[134 + i]) fprintf(stderr, " %d:%u", i, h[134 + i]);
+    fprintf(stderr, "\n[mg simp group hist]");
+    for (int i = 0; i < 64; ++i)
+      if (h[i]) fprintf(stderr, " %d:%u", i, h[i]);
+    fprintf(stderr, "\n[mg simp subs hist]");
+    for (int i = 0; i < 64; ++i)
+      if (h[64 + i]) fprintf(stderr, " %d:%u", i, h[64 + i]);
+    fprintf(stderr, "\n");
+  }
+  return 0;
+}
+
+// The per-label kernel, one workgroup per label, in three nv bands:
+//   nv <= 2048          CAPV=2048 on the main stream
+//   2048 < nv <= 4096   CAPV=4096 (64 KB LDS, 2 blocks/CU) on stream2 —
+//                       these used to fall into the global-array mode
+//                       whose hot per-vertex atomics serialize on L2 lines
+//   nv > 4096           CAPV=2048 (global-array mode) on stream2
+// stream2's bands run concurrently with the main band.
+static int simp_launch_labels(mg_ctx *c, const SimpCall &k) {
+  hipStream_t s = c->stream;
+  auto launch_band = [&](auto fn, hipStream_t st, uint32_t nv_lo,
+                         uint32_t nv_hi) {
+    hipLaunchKernelGGL(fn, dim3((uint32_t)k.L), dim3(256), 0, st,
+                       (uint32_t *)c->faces.ptr,
+                       (uint32_t *)c->simp_faces_alt.ptr,
+                       (const uint32_t *)c->tri_off.ptr,
+                       (const uint32_t *)c->vbase.ptr,
+                       (float *)c->verts.ptr, (float *)c->simp_Q.ptr,
+                       (unsigned long long *)c->simp_pick.ptr,
+                       (uint32_t *)c->simp_remap.ptr,
+                       (uint32_t *)c->simp_deg.ptr,
+                       (uint32_t *)c->simp_adj.ptr,
+                       (uint32_t *)c->simp_pk.ptr,
+                       (SimpPlane *)c->simp_fq.ptr,
+                       (uint8_t *)c->simp_valid.ptr,
+                       k.nt_cur, k.target, k.active,
+                       (uint32_t *)c->simp_park.ptr, k.d_prof, k.d_rh,
+                       k.max_cost, (uint32_t)k.L, SIMP_BIG_CAP, k.env.subs,
+                       nv_lo, nv_hi, 0u, 0xFFFFFFFFu,
+                       (uint32_t *)c->simp_accept.ptr, k.env.propose,
+                       (const uint32_t *)nullptr);
+  };
+  // record BEFORE enqueuing the main band: stream2 must wait only for the
+  // shared setup, so its bands run CONCURRENT with the main one
+  // (recording after it serialized them — 51 ms vs 38 ms overlapped)
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_FORK], s), 40);
+  HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SIMP_FORK], 0), 40);
+  launch_band(k_simplify_label<false, 256, 2048>, s, 0u, 2048u);
+  launch_band(k_simplify_label<false, 256, 4096>, c->stream2, 2048u, 4096u);
+  launch_band(k_simplify_label<false, 256, 2048>, c->stream2, 4096u,
+              0xFFFFFFFFu);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_JOIN], c->stream2), 40);
+  HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_SIMP_JOIN], 0), 40);
+  HIP_TRY(c, hipGetLastError(), 40);
+  return simp_print_diagnostics(c, k);
+}
+
+// Park the faces of labels that are not active: flag the faces of active
+// labels, scan, scatter the others into the park store (simp_park) and
+// compact the flagged ones into the alt face/label arrays.
+//   p_T != null: read the surviving count back into *p_T and make the alt
+//                arrays current (a sync point);
+//   p_T == null: the force-park — nothing survives, nothing is swapped.
+static int park_inactive(mg_ctx *c, const SimpCall &k, uint64_t T,
+                         const char *err_size, const char *err_run, int rc,
+                         uint64_t *p_T) {
+  hipStream_t s = c->stream;
+  const dim3 nb(simp_blocks(T)), blk(SIMP_BLK);
+  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
+  uint32_t *flab = (uint32_t *)c->simp_flab.ptr;
+  uint32_t *keep = (uint32_t *)c->simp_keep.ptr;
+  uint32_t *keep_scan = (uint32_t *)c->simp_keep_scan.ptr;
+  hipLaunchKernelGGL(k_flag_active_faces, nb, blk, 0, s, flab, k.active,
+                     keep, T);
+  if (int e = scan_u32(c, keep, keep_scan, T, s, err_size, err_run, rc))
+    return e;
+  hipLaunchKernelGGL(k_first_label_idx, nb, blk, 0, s, flab,
+                     (uint32_t *)c->simp_first.ptr, T);
+  hipLaunchKernelGGL(k_park_scatter, nb, blk, 0, s, faces_g, flab,
+                     (const uint32_t *)keep, (const uint32_t *)keep_scan,
+                     (const uint32_t *)c->simp_first.ptr,
+                     (const uint32_t *)c->tri_off.ptr,
+                     (uint32_t *)c->simp_faces_alt.ptr,
+                     (uint32_t *)c->simp_flab_alt.ptr,
+                     (uint32_t *)c->simp_park.ptr, SIMP_BIG_CAP, T);
+  if (!p_T) {
+    HIP_TRY(c, hipGetLastError(), rc);
+    return 0;
+  }
+  uint32_t *d_total = (uint32_t *)c->lh_misc.ptr + 4;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
+                     (const uint32_t *)keep_scan, (const uint32_t *)keep, T,
+                     d_total);
+  uint32_t act_total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&act_total, d_total, 4, hipMemcpyDeviceToHost,
+                            s), rc);
+  HIP_TRY(c, hipStreamSynchronize(s), rc);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->simp_flab, c->simp_flab_alt);
+  *p_T = act_total;
+  return 0;
+}
+
+// One round of the global (big-label) path over the T working faces:
+// quadrics, matched-pair collapse, compaction, then parking of the labels
+// that just went inactive. *p_done is set when no label is active any
+// more or no face survives the compaction.
+//
+// One collapse pass per quadric recompute: the same group structure as
+// the per-label kernel and the oracle, but measured on 512^3/200 big
+// labels sub-rounds > 1 are ~5% SLOWER here (the T- and V-sized sub
+// passes dwarf the recompute they skip, unlike the per-label kernel), so
+// the contract pins big labels at 1 sub/group — hence k_update_active's
+// constant 1u.
+static int simp_global_round(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
+                             bool *p_done) {
+  hipStream_t s = c->stream;
+  const dim3 blk(SIMP_BLK), nbl((uint32_t)((k.L + 255) / 256));
+  const uint64_t T = *p_T, V = k.V;
+  // any label still active?
+  HIP_TRY(c, hipMemsetAsync(k.d_any, 0, 4, s), 41);
+  hipLaunchKernelGGL(k_any_active, nbl, dim3(256), 0, s, k.active,
+                     (uint32_t)k.L, k.d_any);
+  uint32_t any = 0;
+  HIP_TRY(c, hipMemcpyAsync(&any, k.d_any, 4, hipMemcpyDeviceToHost, s), 41);
+  HIP_TRY(c, hipStreamSynchronize(s), 41);
+  if (!any) {
+    *p_done = true;
+    return 0;
+  }
+
+  const dim3 nbt(simp_blocks(T)), nbv(simp_blocks(V));
+  const uint64_t NP = 3 * T;
+  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
+  float *verts = (float *)c->verts.ptr;
+  uint32_t *flab = (uint32_t *)c->simp_flab.ptr;
+  unsigned long long *pick = (unsigned long long *)c->simp_pick.ptr;
+  uint32_t *remap = (uint32_t *)c->simp_remap.ptr;
+  uint32_t *accept = (uint32_t *)c->simp_accept.ptr;
+  uint32_t *keep = (uint32_t *)c->simp_keep.ptr;
+  uint32_t *keep_scan = (uint32_t *)c->simp_keep_scan.ptr;
+  float *Q = (float *)c->simp_Q.ptr;
+
+  hipLaunchKernelGGL(k_face_planes, nbt, blk, 0, s, faces_g, verts, k.active,
+                     flab, (SimpPlane *)c->simp_fq.ptr,
+                     (uint8_t *)c->simp_valid.ptr, T);
+  hipLaunchKernelGGL(k_emit_vf_pairs, nbt, blk, 0, s, faces_g, k.active, flab,
+                     (uint32_t *)c->simp_pk.ptr, (uint32_t *)c->simp_pv.ptr,
+                     T);
+  // stable sort pairs by vertex (face order preserved within vertex)
+  {
+    rocprim::double_buffer<uint32_t> dk((uint32_t *)c->simp_pk.ptr,
+                                        (uint32_t *)c->simp_pk_alt.ptr);
+    rocprim::double_buffer<uint32_t> dv((uint32_t *)c->simp_pv.ptr,
+                                        (uint32_t *)c->simp_pv_alt.ptr);
+    if (int e = sort_pairs(c, dk, dv, NP, 0u, 32u, s,
+                           "simplify sort size query", "simplify sort", 42))
+      return e;
+    hipLaunchKernelGGL(k_accum_quadrics, dim3(simp_blocks(NP)), blk, 0, s,
+                       dk.current(), dv.current(),
+                       (const SimpPlane *)c->simp_fq.ptr,
+                       (const uint8_t *)c->simp_valid.ptr, Q, NP);
+  }
+  HIP_TRY(c, hipMemsetAsync(pick, 0xFF, V * 8, s), 43);
+  if (k.env.propose) HIP_TRY(c, hipMemsetAsync(accept, 0xFF, V * 4, s), 43);
+  hipLaunchKernelGGL(k_edge_pick, nbt, blk, 0, s, faces_g, k.active, flab,
+                     (const uint32_t *)c->vbase.ptr, verts, (const float *)Q,
+                     pick, k.max_cost, T);
+  hipLaunchKernelGGL(k_iota, nbv, blk, 0, s, remap, V);
+  hipLaunchKernelGGL(k_collapse, nbv, blk, 0, s, pick, verts, remap, Q, V);
+  if (k.env.propose) {
+    hipLaunchKernelGGL(k_propose, nbv, blk, 0, s,
+                       (const unsigned long long *)pick, accept, V);
+    hipLaunchKernelGGL(k_accept, nbv, blk, 0, s,
+                       (const unsigned long long *)pick,
+                       (const uint32_t *)accept, verts, remap, Q, V);
+  }
+  hipLaunchKernelGGL(k_remap_faces, nbt, blk, 0, s, faces_g,
+                     (const uint32_t *)remap, keep, T);
+  if (int e = scan_u32(c, keep, keep_scan, T, s, "keep scan size query",
+                       "keep scan", 44))
+    return e;
+  uint32_t *d_kept = (uint32_t *)c->lh_misc.ptr + 4;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
+                     (const uint32_t *)keep_scan, (const uint32_t *)keep, T,
+                     d_kept);
+  uint32_t kept = 0;
+  HIP_TRY(c, hipMemcpyAsync(&kept, d_kept, 4, hipMemcpyDeviceToHost, s), 44);
+  HIP_TRY(c, hipMemsetAsync(k.nt_new, 0, k.L * 4, s), 44);
+  hipLaunchKernelGGL(k_compact_faces, nbt, blk, 0, s, faces_g, flab,
+                     (const uint32_t *)keep, (const uint32_t *)keep_scan,
+                     (uint32_t *)c->simp_faces_alt.ptr,
+                     (uint32_t *)c->simp_flab_alt.ptr, k.nt_new, T);
+  hipLaunchKernelGGL(k_update_active, nbl, dim3(256), 0, s, k.nt_new,
+                     k.nt_cur, k.target, k.active, k.d_any, (uint32_t)k.L,
+                     1u);
+  HIP_TRY(c, hipGetLastError(), 44);
+  HIP_TRY(c, hipStreamSynchronize(s), 44);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->simp_flab, c->simp_flab_alt);
+  *p_T = kept;
+  if (kept == 0) {
+    *p_done = true;
+    return 0;
+  }
+  // park faces of labels that just went inactive: working set keeps
+  // only active labels (late rounds touch only the active tail)
+  return park_inactive(c, k, kept, "park scan size query", "park scan", 47,
+                       p_T);
+}
+
+// Final face array (per-label slices gathered from the park store in
+// label-id order), then drop unreferenced vertices (stable) and
+// re-localize the faces. *p_T / *p_V = the final totals.
+static int simp_finalize(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
+                         uint64_t *p_V) {
+  hipStream_t s = c->stream;
+  const dim3 blk(SIMP_BLK);
+  const uint64_t L = k.L, V = k.V;
+  uint32_t *troff_final = (uint32_t *)c->simp_troff_final.ptr;
+  if (int e = scan_u32(c, k.nt_cur, troff_final, L, s,
+                       "final troff scan size", "final troff scan", 49))
+    return e;
+  uint32_t *d_total = (uint32_t *)c->lh_misc.ptr + 6;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
+                     (const uint32_t *)troff_final, k.nt_cur, L, d_total);
+  HIP_TRY(c, hipMemcpyAsync(troff_final + L, d_total, 4,
+                            hipMemcpyDeviceToDevice, s), 49);
+  uint32_t final_total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&final_total, d_total, 4, hipMemcpyDeviceToHost,
+                            s), 49);
+  HIP_TRY(c, hipStreamSynchronize(s), 49);
+  const uint64_t T = final_total;
+  if (T > 0)
+    hipLaunchKernelGGL(k_gather_final, dim3(simp_blocks(T)), blk, 0, s,
+                       (const uint32_t *)c->simp_park.ptr,
+                       (const uint32_t *)c->tri_off.ptr,
+                       (const uint32_t *)troff_final,
+                       (uint32_t *)c->faces.ptr,
+                       (uint32_t *)c->simp_flab.ptr, (uint32_t)L, T);
+  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
+  std::swap(c->tri_off, c->simp_troff_final);
+
+  if (ensure(c, c->simp_ref, (V + 1) * 4)) return 45;
+  if (ensure(c, c->simp_verts_alt, V * 12 + 12)) return 45;
+  if (ensure(c, c->simp_vbase_alt, (L + 1) * 4)) return 45;
+  uint32_t *ref = (uint32_t *)c->simp_ref.ptr;
+  uint32_t *newid = (uint32_t *)c->vtx_scan.ptr;  // NC*4 >= V*4, free now
+  HIP_TRY(c, hipMemsetAsync(ref, 0, V * 4, s), 45);
+  if (T > 0)
+    hipLaunchKernelGGL(k_mark_ref, dim3(simp_blocks(3 * T)), blk, 0, s,
+                       faces_g, ref, 3 * T);
+  if (int e = scan_u32(c, ref, newid, V, s, "ref scan size query",
+                       "ref scan", 45))
+    return e;
+  uint32_t *d_newV = (uint32_t *)c->lh_misc.ptr + 5;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, newid, ref, V,
+                     d_newV);
+  uint32_t newV = 0;
+  HIP_TRY(c, hipMemcpyAsync(&newV, d_newV, 4, hipMemcpyDeviceToHost, s), 45);
+  HIP_TRY(c, hipStreamSynchronize(s), 45);
+  hipLaunchKernelGGL(k_scatter_verts, dim3(simp_blocks(V)), blk, 0, s,
+                     (float *)c->verts.ptr, ref, newid,
+                     (float *)c->simp_verts_alt.ptr, V);
+  hipLaunchKernelGGL(k_new_vbase, dim3((uint32_t)((L + 2 + 255) / 256)),
+                     dim3(256), 0, s, (const uint32_t *)c->vbase.ptr, newid,
+                     (uint32_t *)c->simp_vbase_alt.ptr, (uint32_t)L, newV);
+  if (T > 0)
+    hipLaunchKernelGGL(k_localize_faces, dim3(simp_blocks(T)), blk, 0, s,
+                       faces_g, newid, (const uint32_t *)c->simp_flab.ptr,
+                       (const uint32_t *)c->simp_vbase_alt.ptr,
+                       (uint32_t *)c->simp_faces_alt.ptr, T);
+  HIP_TRY(c, hipGetLastError(), 46);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->verts, c->simp_verts_alt);
+  std::swap(c->vbase, c->simp_vbase_alt);
+  *p_T = T;
+  *p_V = newV;
+  return 0;
+}
+
+// Simplify every label of the welded mesh in the ctx (faces / verts /
+// vbase / tri_off, label per face in lab_sorted). Updates those buffers;
+// p_T/p_V become the post-simplification totals.
+static int run_simplify(mg_ctx *c, uint32_t nlabels,
+                        const uint32_t *lab_sorted,
+                        uint32_t reduction_factor, float max_error,
+                        uint64_t *p_T, uint64_t *p_V) {
+  hipStream_t s = c->stream;
+  uint64_t T = *p_T;
+  if (T == 0 || *p_V == 0) return 0;
+  SimpCall k = {};
+  k.env = read_simp_env();
+  k.L = nlabels;
+  k.V = *p_V;
+  k.max_cost = max_error * max_error;
+  if (int e = simp_alloc(c, k, T)) return e;
+
+  // faces -> global vertex ids, label per face
+  hipLaunchKernelGGL(k_globalize_faces, dim3(simp_blocks(T)), dim3(SIMP_BLK),
+                     0, s, (uint32_t *)c->faces.ptr, lab_sorted,
+                     (const uint32_t *)c->vbase.ptr,
+                     (uint32_t *)c->simp_flab.ptr, T);
+  hipLaunchKernelGGL(k_init_simplify, dim3((uint32_t)((k.L + 255) / 256)),
+                     dim3(256), 0, s, (const uint32_t *)c->tri_off.ptr,
+                     k.nt_cur, k.target, k.active, reduction_factor,
+                     (uint32_t)k.L);
+  HIP_TRY(c, hipGetLastError(), 40);
+
+  if (k.env.prof) {
+    k.d_prof = (unsigned long long *)c->lh_misc.ptr + 8;
+    HIP_TRY(c, hipMemsetAsync(k.d_prof, 0, 48, s), 40);
+  }
+  if (k.env.roundhist) {  // groups/subs per label
+    if (ensure(c, c->simp_rh, 176 * 4)) return 40;
+    k.d_rh = (uint32_t *)c->simp_rh.ptr;
+    HIP_TRY(c, hipMemsetAsync(k.d_rh, 0, 176 * 4, s), 40);
+  }
+  if (int e = simp_launch_labels(c, k)) return e;
+
+  // drop the per-label-kernel labels from the working set; park big
+  // never-active labels (their final faces are their originals)
+  if (int e = park_inactive(c, k, T, "prepark scan size", "prepark scan", 50,
+                            &T))
+    return e;
+
+  bool done = false;
+  for (int group = 0; group < 65536 && !done; ++group)
+    if (int e = simp_global_round(c, k, &T, &done)) return e;
+
+  // any faces still in the working set (round-cap exit): force-park them
+  if (T > 0) {
+    HIP_TRY(c, hipMemsetAsync(k.active, 0, k.L, s), 48);
+    if (int e = park_inactive(c, k, T, "force-park scan size query",
+                              "force-park scan", 48, nullptr))
+      return e;
+  }
+  if (int e = simp_finalize(c, k, &T, p_V)) return e;
+  *p_T = T;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// one chunk: the stage functions in pipeline order, then mesh_chunk_impl
+
+// Label map table cap: above this the caller preprocesses on the host.
+#define MG_MAP_MAX_ENTRIES (1ull << 24)
+
+// Per-call values of one mesh_chunk_impl, filled in as the stages run.
+struct ChunkCall {
+  int sx, sy, sz, dtype;
+  size_t esize;
+  uint64_t nvox;
+  GridDims g;
+  float rx, ry, rz;
+  int voxel_centered;
+  uint32_t nlabels;        // run_count_emit
+  uint64_t T;              // triangles (run_count_emit; run_simplify)
+  uint64_t V;              // vertices (run_weld; run_simplify)
+  // run_partition: label id per triangle (the sort's key output), the
+  // 8-B records the weld reads and the permutation to read them through
+  // (null when the records themselves were sorted), the slot triples
+  uint32_t *lab_sorted;
+  const uint2 *rec_src;
+  const uint32_t *order_sorted;
+  uint32_t *corner_ent;
+};
+
+static void set_hole_stash(mg_ctx *c, const ChunkCall &k) {
+  c->holes_valid = true;
+  c->holes_sx = k.sx; c->holes_sy = k.sy; c->holes_sz = k.sz;
+  c->holes_dtype = k.dtype;
+}
+
+// H2D (skipped when the caller staged the identical volume already)
+static int upload_labels(mg_ctx *c, const ChunkCall &k,
+                         const void *labels_host, uint32_t flags) {
+  const size_t bytes = k.nvox * k.esize;
+  if ((flags & MG_FLAG_SKIP_H2D) && c->labels.cap >= bytes) return 0;
+  if (ensure(c, c->labels, bytes)) return 11;
+  HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels_host, bytes,
+                            hipMemcpyHostToDevice, c->stream), 11);
+  return 0;
+}
+
+// device dust removal (three volume passes; see k_dust_* above)
+static int run_dust(mg_ctx *c, const ChunkCall &k, uint64_t dust_threshold) {
+  hipStream_t s = c->stream;
+  uint32_t ndl = 0;
+  if (int e = hash_volume_labels(c, k.dtype, k.nvox, " (dust)", 16, &ndl))
+    return e;
+  if (ndl == 0) return 0;
+  const LabelHash lh = label_hash_view(c);
+  if (ensure(c, c->order, (uint64_t)ndl * 4)) return 16;
+  HIP_TRY(c, hipMemsetAsync(c->order.ptr, 0, (uint64_t)ndl * 4, s), 16);
+  by_dtype(k.dtype, [&](auto t) {
+    using T = decltype(t);
+    const dim3 nb(4096), blk(256);
+    hipLaunchKernelGGL(k_dust_count<T>, nb, blk, 0, s,
+                       (const T *)c->labels.ptr, k.nvox, lh,
+                       (uint32_t *)c->order.ptr);
+    hipLaunchKernelGGL(k_dust_zero<T>, nb, blk, 0, s, (T *)c->labels.ptr,
+                       k.nvox, lh, (const uint32_t *)c->order.ptr,
+                       dust_threshold);
+  });
+  HIP_TRY(c, hipGetLastError(), 16);
+  return 0;
+}
+
+// label map in place on the resident labels (after dust, which counted
+// the RAW labels — the reference's order, mesh.py:193-204)
+static int run_label_map(mg_ctx *c, const ChunkCall &k,
+                         const mg_label_map *map) {
+  hipStream_t s = c->stream;
+  const uint64_t n = map->n, nvox = k.nvox;
+  MapTable mt;
+  mt.nslots = next_pow2_u64(std::max<uint64_t>(2 * n, 64));
+  if (ensure(c, c->map_tab, mt.nslots * 16)) return 41;
+  if (ensure(c, c->lh_misc, 256)) return 41;
+  mt.slots = (ulonglong2 *)c->map_tab.ptr;
+  uint32_t *d_err = (uint32_t *)c->lh_misc.ptr + 2;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_MAP_START], s), 41);
+  HIP_TRY(c, hipMemsetAsync(c->map_tab.ptr, 0, mt.nslots * 16, s), 41);
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, s), 41);
+  if (n > 0) {
+    if (ensure(c, c->map_keys, n * 8)) return 41;
+    if (ensure(c, c->map_vals, n * 8)) return 41;
+    HIP_TRY(c, hipMemcpyAsync(c->map_keys.ptr, map->keys, n * 8,
+                              hipMemcpyHostToDevice, s), 41);
+    HIP_TRY(c, hipMemcpyAsync(c->map_vals.ptr, map->vals, n * 8,
+                              hipMemcpyHostToDevice, s), 41);
+    const int bblk = 256;
+    hipLaunchKernelGGL(k_map_build, dim3((uint32_t)((n + bblk - 1) / bblk)),
+                       dim3(bblk), 0, s, (const uint64_t *)c->map_keys.ptr,
+                       (const uint64_t *)c->map_vals.ptr, n, mt, d_err);
+  }
+  const uint64_t nvec = nvox / (16 / k.esize);
+  const uint32_t miss_zero = map->miss == MG_MAP_MISS_ZERO;
+  // MG_MAP_LDS=0 reverts small tables to the L2-probed kernel (A/B)
+  static const bool use_lds = []() {
+    const char *e = getenv("MG_MAP_LDS");
+    return !(e && e[0] == '0');
+  }();
+  const bool lds = use_lds && n <= MAP_LDS_MAX_ENTRIES;
+  const int mblk = lds ? MAP_LDS_BLOCK : 256;
+  const uint32_t mnb = (uint32_t)std::min<uint64_t>(
+      std::max<uint64_t>((nvec + mblk - 1) / mblk, 1), lds ? 512 : 4096);
+  by_dtype(k.dtype, [&](auto t) {
+    using T = decltype(t);
+    if (lds)  // LDS copy of the table: <= 4096 slots = 64 KB
+      hipLaunchKernelGGL(k_label_map_lds<T>, dim3(mnb), dim3(mblk),
+                         mt.nslots * 16, s, (T *)c->labels.ptr, nvox, mt,
+                         miss_zero);
+    else
+      hipLaunchKernelGGL(k_label_map<T>, dim3(mnb), dim3(mblk), 0, s,
+                         (T *)c->labels.ptr, nvox, mt, miss_zero);
+  });
+  HIP_TRY(c, hipGetLastError(), 41);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_MAP_END], s), 41);
+  uint32_t map_err = 0;
+  HIP_TRY(c, hipMemcpyAsync(&map_err, d_err, 4, hipMemcpyDeviceToHost, s),
+          41);
+  HIP_TRY(c, hipStreamSynchronize(s), 41);
+  if (map_err & MAP_ERR_DUPLICATE) {
+    SET_ERR(c, "label map: duplicate key among %llu entries",
+            (unsigned long long)n);
+    return 42;
+  }
+  if (map_err) {
+    SET_ERR(c, "label map: table build failed (flag %u)", map_err);
+    return 42;
+  }
+  c->stats.ms_labelmap = ev_ms(c, EV_MAP_START, EV_MAP_END);
+  return 0;
+}
+
+// grid of the wave-per-segment kernels (k_count, k_emit)
+static inline uint32_t seg_blocks(const GridDims &g, int blk) {
+  const int waves_per_blk = blk / WAVE;
+  int64_t nb = std::min<int64_t>(
+      (g.nseg + waves_per_blk - 1) / waves_per_blk, 8192);
+  return (uint32_t)((nb + 7) & ~7ll);  // multiple of 8: XCD slab schedule
+}
+
+// [1] count + label hash build, [2] scan. *p_overflow: the hash was too
+// small and the pass must be repeated with a bigger one.
+static int count_pass(mg_ctx *c, ChunkCall &k, bool *p_overflow) {
+  hipStream_t s = c->stream;
+  const LabelHash lh = label_hash_view(c);
+  uint32_t *d_segcnt = (uint32_t *)c->segcnt.ptr;
+  uint32_t *d_segoff = (uint32_t *)c->segoff.ptr;
+  const int64_t nseg = k.g.nseg;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_H2D_END], s), 30);  // see the enum
+  by_dtype(k.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_count<T>, dim3(seg_blocks(k.g, 256)), dim3(256), 0,
+                       s, (const T *)c->labels.ptr, k.g, d_segcnt, lh);
+  });
+  HIP_TRY(c, hipGetLastError(), 30);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_COUNT_END], s), 30);
+
+  // check overflow + read label count
+  uint32_t misc[2] = {0, 0};
+  HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8, hipMemcpyDeviceToHost, s),
+          30);
+  // scan segcnt -> segoff
+  if (int e = scan_u32(c, d_segcnt, d_segoff, (size_t)nseg, s,
+                       "seg scan size query failed", "seg scan failed", 30))
+    return e;
+  uint32_t last_off = 0, last_cnt = 0;
+  HIP_TRY(c, hipMemcpyAsync(&last_off, d_segoff + (nseg - 1), 4,
+                            hipMemcpyDeviceToHost, s), 30);
+  HIP_TRY(c, hipMemcpyAsync(&last_cnt, d_segcnt + (nseg - 1), 4,
+                            hipMemcpyDeviceToHost, s), 30);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SCAN_END], s), 30);
+  HIP_TRY(c, hipStreamSynchronize(s), 30);
+  *p_overflow = misc[1] != 0;
+  k.nlabels = misc[0];
+  k.T = (uint64_t)last_off + last_cnt;
+  return 0;
+}
+
+// [1]-[3]: count (grow-and-retry on label hash overflow), scan, label
+// values, emit. Leaves k.nlabels / k.T; emits nothing when either is 0.
+static int run_count_emit(mg_ctx *c, ChunkCall &k) {
+  hipStream_t s = c->stream;
+  if (ensure(c, c->segcnt, k.g.nseg * 4)) return 12;
+  if (ensure(c, c->segoff, k.g.nseg * 4)) return 12;
+  for (;;) {
+    if (int e = label_hash_reset(c, 12)) return e;
+    bool overflow = false;
+    if (int e = count_pass(c, k, &overflow)) return e;
+    if (!overflow) break;
+    if (int e = label_hash_grow(c, "", 13)) return e;
+  }
+  c->stats.total_tris = k.T;
+  c->stats.n_labels = k.nlabels;
+  if (k.T == 0 || k.nlabels == 0) return 0;
+  if (k.T > (1ull << 31) / 3 * 2) {  // 3T must fit u32 stream index
+    SET_ERR(c, "chunk produces %llu triangles (> corner-index limit); "
+            "split the task shape", (unsigned long long)k.T);
+    return 15;
+  }
+  if (k.nlabels >= (1u << 27)) {  // label id shares the 64-bit weld key
+    SET_ERR(c, "%u labels exceed the 2^27 per-chunk label limit", k.nlabels);
+    return 15;
+  }
+  const LabelHash lh = label_hash_view(c);
+  // label id -> value
+  if (ensure(c, c->label_values, (uint64_t)k.nlabels * 8)) return 17;
+  hipLaunchKernelGGL(k_label_values,
+                     dim3((uint32_t)((c->lh_slots + 255) / 256)), dim3(256),
+                     0, s, lh, (uint64_t *)c->label_values.ptr, c->lh_slots);
+  // [3] emit
+  if (ensure(c, c->tri_label, k.T * 4)) return 18;
+  if (ensure(c, c->tri_keys, k.T * 8)) return 18;
+  by_dtype(k.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_emit<T>, dim3(seg_blocks(k.g, 256)), dim3(256), 0, s,
+                       (const T *)c->labels.ptr, k.g,
+                       (const uint32_t *)c->segoff.ptr, lh,
+                       (uint32_t *)c->tri_label.ptr,
+                       (uint2 *)c->tri_keys.ptr);
+  });
+  HIP_TRY(c, hipGetLastError(), 18);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_EMIT_END], s), 18);
+  return 0;
+}
+
+// [4] stable partition by label id. Default (MG_SORT_RECS=0 reverts):
+// the 8-B records ride the radix sort as its 64-bit VALUES, so the
+// weld insert reads them back SEQUENTIALLY instead of paying a
+// random 8-B gather through the permutation.
+static int run_partition(mg_ctx *c, ChunkCall &k) {
+  hipStream_t s = c->stream;
+  const uint64_t T = k.T;
+  const char *sre = getenv("MG_SORT_RECS");
+  const bool sort_recs = !(sre && sre[0] == '0');
+  if (ensure(c, c->keys_sorted, T * 20)) return 19;  // [sort-alt 8B] + [slot triples 12B]
+  if (ensure(c, c->tri_label_alt, T * 4)) return 19;
+  k.corner_ent = (uint32_t *)c->keys_sorted.ptr + 2 * T;
+  const dim3 nb((uint32_t)((T + 255) / 256)), blk(256);
+  unsigned end_bit = 1;
+  while ((1u << end_bit) < k.nlabels) ++end_bit;
+  rocprim::double_buffer<uint32_t> d_keys(
+      (uint32_t *)c->tri_label.ptr, (uint32_t *)c->tri_label_alt.ptr);
+  if (sort_recs) {
+    rocprim::double_buffer<uint64_t> d_vals(
+        (uint64_t *)c->tri_keys.ptr, (uint64_t *)c->keys_sorted.ptr);
+    if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
+                           "radix_sort size query failed",
+                           "radix_sort failed", 19))
+      return e;
+    k.rec_src = (const uint2 *)d_vals.current();
+    k.order_sorted = nullptr;  // records already label-partitioned
+  } else {
+    if (ensure(c, c->order, T * 4)) return 19;
+    if (ensure(c, c->order_alt, T * 4)) return 19;
+    hipLaunchKernelGGL(k_iota, nb, blk, 0, s, (uint32_t *)c->order.ptr, T);
+    rocprim::double_buffer<uint32_t> d_vals(
+        (uint32_t *)c->order.ptr, (uint32_t *)c->order_alt.ptr);
+    if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
+                           "radix_sort size query failed",
+                           "radix_sort failed", 19))
+      return e;
+    k.rec_src = (const uint2 *)c->tri_keys.ptr;
+    k.order_sorted = d_vals.current();
+  }
+  k.lab_sorted = d_keys.current();
+  // label ranges
+  if (ensure(c, c->tri_off, ((uint64_t)k.nlabels + 1) * 4)) return 19;
+  hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.lab_sorted,
+                     (uint32_t *)c->tri_off.ptr, T, k.nlabels);
+  HIP_TRY(c, hipGetLastError(), 19);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_PARTITION_END], s), 19);
+  return 0;
+}
+
+// [5] weld — direct-addressed (edge, side) table, collision-free
+static int run_weld(mg_ctx *c, ChunkCall &k) {
+  hipStream_t s = c->stream;
+  const uint64_t T = k.T, NC = 3 * T;  // corners
+  const uint64_t wslots = 6 * k.nvox;  // 3 edges/voxel x 2 sides
+  if (wslots >= (1ull << 32)) {
+    SET_ERR(c, "chunk too large for the 32-bit weld table (%d x %d x %d); "
+            "split the task shape (the reference's own mesher bound is "
+            "1023x1023x511, igneous_cli/cli.py:1049-1052)", k.sx, k.sy, k.sz);
+    return 20;
+  }
+  if (ensure(c, c->wh_keys, wslots * 4)) return 20;   // wminp
+  if (ensure(c, c->vtx_scan, NC * 4)) return 20;
+  HIP_TRY(c, hipMemsetAsync(c->wh_keys.ptr, 0, wslots * 4, s), 20);
+  uint32_t *wminp = (uint32_t *)c->wh_keys.ptr;
+  // slot triples; the flag pass turns non-first entries into first positions
+  uint32_t *corner_ent = k.corner_ent;
+  const dim3 nbt((uint32_t)((T + 255) / 256)), blk(256);
+  hipLaunchKernelGGL((k_weld_insert<1024, 2>),
+                     dim3((uint32_t)((T + 2047) / 2048)), dim3(1024), 0, s,
+                     k.rec_src, k.order_sorted, corner_ent, wminp, k.g.sx,
+                     k.g.sx * k.g.sy, T);
+  // first-occurrence flags as a bit array + word-granular scan
+  // (the vtx_scan buffer is NC*4 bytes >= nwords*12)
+  const uint64_t nwords = (NC + 63) / 64;
+  unsigned long long *bits = (unsigned long long *)c->vtx_scan.ptr;
+  uint32_t *wscan = (uint32_t *)c->vtx_scan.ptr + 2 * nwords;
+  hipLaunchKernelGGL(k_weld_flag_bits,
+                     dim3((uint32_t)((nwords * 64 + 255) / 256)), blk, 0, s,
+                     corner_ent, wminp, bits, NC, nwords);
+  if (int e = scan_u32(c, rocprim::make_transform_iterator(bits, PopcWord{}),
+                       wscan, nwords, s, "weld scan size query failed",
+                       "weld scan failed", 20))
+    return e;
+  uint32_t *d_tv = (uint32_t *)c->lh_misc.ptr + 3;
+  hipLaunchKernelGGL(k_total_verts, dim3(1), dim3(1), 0, s, wscan, bits,
+                     nwords, d_tv);
+  uint32_t tv = 0;
+  HIP_TRY(c, hipMemcpyAsync(&tv, d_tv, 4, hipMemcpyDeviceToHost, s), 21);
+  HIP_TRY(c, hipStreamSynchronize(s), 21);
+  k.V = tv;
+  c->stats.total_verts = tv;
+
+  if (ensure(c, c->verts, k.V * 12)) return 22;
+  if (ensure(c, c->faces, NC * 4)) return 22;
+  if (ensure(c, c->vbase, ((uint64_t)k.nlabels + 1) * 4)) return 22;
+  // vbase depends only on the scan, so it goes first
+  hipLaunchKernelGGL(k_vbase, dim3((k.nlabels + 1 + 255) / 256), dim3(256),
+                     0, s, (const uint32_t *)c->tri_off.ptr,
+                     (const uint32_t *)wscan,
+                     (const unsigned long long *)bits,
+                     (uint32_t *)c->vbase.ptr, k.nlabels, k.V);
+  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s, corner_ent,
+                     k.lab_sorted, (const uint32_t *)wscan,
+                     (const unsigned long long *)bits,
+                     (const uint32_t *)c->vbase.ptr, (float *)c->verts.ptr,
+                     (uint32_t *)c->faces.ptr, (uint32_t)k.g.sx,
+                     (uint32_t)(k.g.sx * k.g.sy), k.rx, k.ry, k.rz,
+                     k.voxel_centered ? 0.0f : 0.5f, T);
+  HIP_TRY(c, hipGetLastError(), 22);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_WELD_END], s), 22);
+  return 0;
+}
+
+// [7] D2H of the flat vertex/face arrays into the ctx's pinned staging
+// and the per-label descriptor, meshes by ascending label value. Under
+// MG_FLAG_DEVICE_ONLY nothing is copied and the meshset is empty.
+static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
+                           mg_meshset **out) {
+  hipStream_t s = c->stream;
+  if (flags & MG_FLAG_DEVICE_ONLY) {
+    HIP_TRY(c, hipStreamSynchronize(s), 23);
+    *out = empty_meshset();
+    return 0;
+  }
+  const uint32_t nlabels = k.nlabels;
+  const uint64_t V = k.V, NC = 3 * k.T;
+  if (ensure_host(c, c->h_verts, V * 12 + 12)) return 24;
+  if (ensure_host(c, c->h_faces, NC * 4 + 4)) return 24;
+  float *h_verts = (float *)c->h_verts.ptr;
+  uint32_t *h_faces = (uint32_t *)c->h_faces.ptr;
+  std::vector<uint32_t> h_tri_off(nlabels + 1), h_vbase(nlabels + 1);
+  std::vector<uint64_t> h_label_values(nlabels);
+  if (V > 0)
+    HIP_TRY(c, hipMemcpyAsync(h_verts, c->verts.ptr, V * 12,
+                              hipMemcpyDeviceToHost, s), 24);
+  if (NC > 0)
+    HIP_TRY(c, hipMemcpyAsync(h_faces, c->faces.ptr, NC * 4,
+                              hipMemcpyDeviceToHost, s), 24);
+  HIP_TRY(c, hipMemcpyAsync(h_tri_off.data(), c->tri_off.ptr,
+                            (nlabels + 1) * 4, hipMemcpyDeviceToHost, s), 24);
+  HIP_TRY(c, hipMemcpyAsync(h_vbase.data(), c->vbase.ptr, (nlabels + 1) * 4,
+                            hipMemcpyDeviceToHost, s), 24);
+  HIP_TRY(c, hipMemcpyAsync(h_label_values.data(), c->label_values.ptr,
+                            nlabels * 8, hipMemcpyDeviceToHost, s), 24);
+  HIP_TRY(c, hipStreamSynchronize(s), 24);
+
+  size_t meta_off = sizeof(mg_meshset) + sizeof(mg_mesh) * nlabels;
+  mg_meshset *ms = (mg_meshset *)calloc(1, meta_off + (size_t)nlabels * 24);
+  ms->nmeshes = nlabels;
+  ms->meshes = (mg_mesh *)((char *)ms + sizeof(mg_meshset));
+  ms->verts_base = h_verts;
+  ms->faces_base = h_faces;
+  ms->total_verts = V;
+  ms->total_tris = k.T;
+  ms->labels_arr = (uint64_t *)((char *)ms + meta_off);
+  ms->voff_arr = (uint32_t *)(ms->labels_arr + nlabels);
+  ms->nv_arr = ms->voff_arr + nlabels;
+  ms->foff_arr = ms->nv_arr + nlabels;
+  ms->nf_arr = ms->foff_arr + nlabels;
+  // order meshes by ascending label value
+  std::vector<uint32_t> idx(nlabels);
+  for (uint32_t i = 0; i < nlabels; ++i) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
+    return h_label_values[a] < h_label_values[b];
+  });
+  for (uint32_t m = 0; m < nlabels; ++m) {
+    uint32_t l = idx[m];
+    mg_mesh &mm = ms->meshes[m];
+    mm.label = h_label_values[l];
+    mm.nverts = h_vbase[l + 1] - h_vbase[l];
+    mm.ntris = h_tri_off[l + 1] - h_tri_off[l];
+    mm.verts = h_verts + 3ull * h_vbase[l];
+    mm.faces = h_faces + 3ull * h_tri_off[l];
+    ms->labels_arr[m] = mm.label;
+    ms->voff_arr[m] = h_vbase[l];
+    ms->nv_arr[m] = mm.nverts;
+    ms->foff_arr[m] = h_tri_off[l];
+    ms->nf_arr[m] = mm.ntris;
+  }
+  *out = ms;
+  return 0;
+}
 
 static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            int sx, int sy, int sz, int dtype,
                            float rx, float ry, float rz,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
-                           uint32_t flags_, const mg_label_map *map,
-                           uint32_t fill_level, mg_meshset **out);
+                           uint32_t flags, const mg_label_map *map,
+                           uint32_t fill_level, mg_meshset **out) {
+  ChunkCall k = {};
+  k.sx = sx; k.sy = sy; k.sz = sz; k.dtype = dtype;
+  k.esize = (dtype == MG_U64) ? 8 : 4;
+  k.nvox = (uint64_t)sx * sy * sz;
+  k.rx = rx; k.ry = ry; k.rz = rz;
+  k.voxel_centered = voxel_centered;
+  GridDims &g = k.g;
+  g.sx = sx; g.sy = sy; g.sz = sz;
+  g.ncx = sx > 1 ? sx - 1 : 0;
+  g.ncy = sy > 1 ? sy - 1 : 0;
+  g.ncz = sz > 1 ? sz - 1 : 0;
+  g.nsegx = (g.ncx + WAVE - 1) / WAVE;
+  g.nseg = g.nsegx * g.ncy * g.ncz;
 
-// Label map table cap: above this the caller preprocesses on the host.
-#define MG_MAP_MAX_ENTRIES (1ull << 24)
+  memset(&c->stats, 0, sizeof(c->stats));
+  c->stats.bytes_read_algorithmic = k.nvox * k.esize;
+  hipStream_t s = c->stream;
+
+  // trivial empty-cell-grid case
+  if (g.nseg == 0) {
+    *out = empty_meshset();
+    if (fill_level) set_hole_stash(c, k);  // nothing to mesh there either
+    return 0;
+  }
+
+  HIP_TRY(c, hipEventRecord(c->ev[EV_START], s), 10);
+  if (int e = upload_labels(c, k, labels_host, flags)) return e;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_H2D_END], s), 11);
+  if (dust_threshold > 0)
+    if (int e = run_dust(c, k, dust_threshold)) return e;
+  if (map)
+    if (int e = run_label_map(c, k, map)) return e;
+  // fill_holes on the dusted + mapped labels (mesh.py:211-228): the
+  // resident volume becomes the filled one, the hole volume stays in
+  // c->holes for mg_mesh_holes
+  if (fill_level) {
+    HIP_TRY(c, hipEventRecord(c->ev[EV_FILL_START], s), 56);
+    if (int e = run_fill_holes(c, dtype, sx, sy, sz, fill_level, nullptr))
+      return e;
+    HIP_TRY(c, hipEventRecord(c->ev[EV_FILL_END], s), 56);
+    set_hole_stash(c, k);
+  }
+
+  if (int e = run_count_emit(c, k)) return e;
+  if (k.T == 0 || k.nlabels == 0) {
+    *out = empty_meshset();
+    HIP_TRY(c, hipStreamSynchronize(s), 14);
+    c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
+    if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
+    return 0;
+  }
+  if (int e = run_partition(c, k)) return e;
+  if (int e = run_weld(c, k)) return e;
+  // [6] per-label quadric simplification (mesh.py:376-381 semantics)
+  if (reduction_factor > 1 && k.T > 0)
+    if (int e = run_simplify(c, k.nlabels, k.lab_sorted, reduction_factor,
+                             max_error, &k.T, &k.V))
+      return e;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMPLIFY_END], s), 22);
+  if (int e = extract_meshset(c, k, flags, out)) return e;
+  HIP_TRY(c, hipEventRecord(c->ev[EV_END], s), 25);
+  HIP_TRY(c, hipStreamSynchronize(s), 25);
+
+  c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
+  c->stats.ms_count = ev_ms(c, EV_H2D_END, EV_COUNT_END);
+  c->stats.ms_scan = ev_ms(c, EV_COUNT_END, EV_SCAN_END);
+  c->stats.ms_emit = ev_ms(c, EV_SCAN_END, EV_EMIT_END);
+  c->stats.ms_partition = ev_ms(c, EV_EMIT_END, EV_PARTITION_END);
+  c->stats.ms_weld = ev_ms(c, EV_PARTITION_END, EV_WELD_END);
+  c->stats.ms_simplify = ev_ms(c, EV_WELD_END, EV_SIMPLIFY_END);
+  c->stats.ms_d2h = ev_ms(c, EV_SIMPLIFY_END, EV_END);
+  c->stats.ms_total = ev_ms(c, EV_START, EV_END);
+  if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// C ABI entry points
+
+// dims / dtype checks shared by the calls that take a label volume
+static int check_volume_args(mg_ctx *c, int sx, int sy, int sz, int dtype) {
+  if (sx < 1 || sy < 1 || sz < 1 || sx > 2047 || sy > 2047 || sz > 2047) {
+    SET_ERR(c, "dims out of range (1..2047): %d %d %d", sx, sy, sz);
+    return 2;
+  }
+  if (dtype != MG_U32 && dtype != MG_U64) {
+    SET_ERR(c, "bad dtype %d", dtype);
+    return 3;
+  }
+  return 0;
+}
+
+static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
+                           uint32_t flags) {
+  if (map->miss != MG_MAP_MISS_KEEP && map->miss != MG_MAP_MISS_ZERO) {
+    SET_ERR(c, "label map: bad miss policy %u", map->miss);
+    return 5;
+  }
+  if (flags & MG_FLAG_SKIP_H2D) {
+    SET_ERR(c, "label map cannot be combined with MG_FLAG_SKIP_H2D "
+            "(the resident volume is already mapped)");
+    return 5;
+  }
+  if (map->n > MG_MAP_MAX_ENTRIES) {
+    SET_ERR(c, "label map: %llu entries exceed the %llu-entry cap",
+            (unsigned long long)map->n,
+            (unsigned long long)MG_MAP_MAX_ENTRIES);
+    return 5;
+  }
+  if (map->n > 0 && (!map->keys || !map->vals)) {
+    SET_ERR(c, "label map: null keys/vals with n=%llu",
+            (unsigned long long)map->n);
+    return 5;
+  }
+  for (uint64_t i = 0; i < map->n; ++i) {
+    if (map->keys[i] == 0) {
+      SET_ERR(c, "label map: key 0 at entry %llu (label 0 is never "
+              "looked up)", (unsigned long long)i);
+      return 5;
+    }
+    if (dtype == MG_U32 && map->vals[i] > 0xFFFFFFFFull) {
+      SET_ERR(c, "label map: value %llu at entry %llu does not fit "
+              "MG_U32", (unsigned long long)map->vals[i],
+              (unsigned long long)i);
+      return 5;
+    }
+  }
+  return 0;
+}
+
+extern "C" {
 
 int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
                          int sz, int dtype, float rx, float ry, float rz,
@@ -994,49 +2147,9 @@ int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
   }
   if (!labels || !out) { SET_ERR(c, "null argument"); return 1; }
   c->holes_valid = false;  // a stash belongs to the call just before
-  if (sx < 1 || sy < 1 || sz < 1 || sx > 2047 || sy > 2047 || sz > 2047) {
-    SET_ERR(c, "dims out of range (1..2047): %d %d %d", sx, sy, sz);
-    return 2;
-  }
-  if (dtype != MG_U32 && dtype != MG_U64) {
-    SET_ERR(c, "bad dtype %d", dtype);
-    return 3;
-  }
-  if (map) {
-    if (map->miss != MG_MAP_MISS_KEEP && map->miss != MG_MAP_MISS_ZERO) {
-      SET_ERR(c, "label map: bad miss policy %u", map->miss);
-      return 5;
-    }
-    if (flags & MG_FLAG_SKIP_H2D) {
-      SET_ERR(c, "label map cannot be combined with MG_FLAG_SKIP_H2D "
-              "(the resident volume is already mapped)");
-      return 5;
-    }
-    if (map->n > MG_MAP_MAX_ENTRIES) {
-      SET_ERR(c, "label map: %llu entries exceed the %llu-entry cap",
-              (unsigned long long)map->n,
-              (unsigned long long)MG_MAP_MAX_ENTRIES);
-      return 5;
-    }
-    if (map->n > 0 && (!map->keys || !map->vals)) {
-      SET_ERR(c, "label map: null keys/vals with n=%llu",
-              (unsigned long long)map->n);
-      return 5;
-    }
-    for (uint64_t i = 0; i < map->n; ++i) {
-      if (map->keys[i] == 0) {
-        SET_ERR(c, "label map: key 0 at entry %llu (label 0 is never "
-                "looked up)", (unsigned long long)i);
-        return 5;
-      }
-      if (dtype == MG_U32 && map->vals[i] > 0xFFFFFFFFull) {
-        SET_ERR(c, "label map: value %llu at entry %llu does not fit "
-                "MG_U32", (unsigned long long)map->vals[i],
-                (unsigned long long)i);
-        return 5;
-      }
-    }
-  }
+  if (int e = check_volume_args(c, sx, sy, sz, dtype)) return e;
+  if (map)
+    if (int e = check_label_map(c, map, dtype, flags)) return e;
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return mesh_chunk_impl(c, labels, sx, sy, sz, dtype, rx, ry, rz,
                          reduction_factor, max_error, voxel_centered,
@@ -1052,6 +2165,16 @@ int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
   return mg_mesh_chunk_filled(c, labels, sx, sy, sz, dtype, rx, ry, rz,
                               reduction_factor, max_error, voxel_centered,
                               dust_threshold, flags, map, 0u, out);
+}
+
+int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
+                  int dtype, float rx, float ry, float rz,
+                  uint32_t reduction_factor, float max_error,
+                  int voxel_centered, uint64_t dust_threshold,
+                  uint32_t flags, mg_meshset **out) {
+  return mg_mesh_chunk_mapped(c, labels, sx, sy, sz, dtype, rx, ry, rz,
+                              reduction_factor, max_error, voxel_centered,
+                              dust_threshold, flags, nullptr, out);
 }
 
 int mg_mesh_holes(mg_ctx *c, float rx, float ry, float rz,
@@ -1088,14 +2211,7 @@ int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,
     SET_ERR(c, "null argument");
     return 1;
   }
-  if (sx < 1 || sy < 1 || sz < 1 || sx > 2047 || sy > 2047 || sz > 2047) {
-    SET_ERR(c, "dims out of range (1..2047): %d %d %d", sx, sy, sz);
-    return 2;
-  }
-  if (dtype != MG_U32 && dtype != MG_U64) {
-    SET_ERR(c, "bad dtype %d", dtype);
-    return 3;
-  }
+  if (int e = check_volume_args(c, sx, sy, sz, dtype)) return e;
   if (level < 1 || level > 2) {
     SET_ERR(c, "fill level %u: only levels 1-2 are implemented (level 3 "
             "needs a multilabel dilation, 4+ a merge threshold)", level);
@@ -1119,1201 +2235,15 @@ int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,
   return 0;
 }
 
-int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
-                  int dtype, float rx, float ry, float rz,
-                  uint32_t reduction_factor, float max_error,
-                  int voxel_centered, uint64_t dust_threshold,
-                  uint32_t flags, mg_meshset **out) {
-  return mg_mesh_chunk_mapped(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                              reduction_factor, max_error, voxel_centered,
-                              dust_threshold, flags, nullptr, out);
-}
-
-}  // extern "C"
-
-template <typename T>
-static int run_count_emit(mg_ctx *c, const T *d_labels, const GridDims &g,
-                          LabelHash lh, uint32_t *d_segcnt,
-                          uint32_t *d_segoff, uint64_t *p_total,
-                          uint32_t *p_nlabels);
-
-static double ev_ms(mg_ctx *c, int a, int b) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->ev[a], c->ev[b]) != hipSuccess) return 0.0;
-  return (double)ms;
-}
-
-
-// ---------------------------------------------------------------------------
-// GPU quadric simplification driver (kernels in simplify.hip); mirrors
-// oracle/simplify.c round for round. Updates faces/verts/vbase/tri_off
-// in the ctx; p_T/p_V become the post-simplification totals.
-static int run_simplify(mg_ctx *c, uint32_t nlabels,
-                        const uint32_t *lab_sorted,
-                        uint32_t reduction_factor, float max_error,
-                        uint64_t *p_T, uint64_t *p_V) {
-  hipStream_t s = c->stream;
-  uint64_t T = *p_T;
-  const uint64_t V = *p_V;
-  const float max_cost = max_error * max_error;
-  const int blk = 256;
-  if (T == 0 || V == 0) return 0;
-
-  // meta layout: [0,L) nt_cur | [L,2L) target | [2L,3L) nt_new |
-  //              3L..: active u8[L] | any u32 (aligned)
-  const uint64_t L = nlabels;
-  const uint64_t meta_bytes = L * 12 + ((L + 3) & ~3ull) + 4;
-  if (ensure(c, c->simp_meta, meta_bytes)) return 40;
-  uint32_t *nt_cur = (uint32_t *)c->simp_meta.ptr;
-  uint32_t *target = nt_cur + L;
-  uint32_t *nt_new = target + L;
-  uint8_t *active = (uint8_t *)(nt_new + L);
-  uint32_t *d_any = (uint32_t *)((char *)c->simp_meta.ptr +
-                                 L * 12 + ((L + 3) & ~3ull));
-
-  if (ensure(c, c->simp_flab, T * 4)) return 40;
-  if (ensure(c, c->simp_flab_alt, T * 4)) return 40;
-  if (ensure(c, c->simp_faces_alt, T * 12)) return 40;
-  if (ensure(c, c->simp_fq, T * sizeof(SimpPlane))) return 40;
-  if (ensure(c, c->simp_valid, T)) return 40;
-  if (ensure(c, c->simp_pk, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pk_alt, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pv, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pv_alt, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_Q, V * 48)) return 40;  // 12-float rows
-  if (ensure(c, c->simp_pick, V * 8)) return 40;
-  if (ensure(c, c->simp_remap, V * 4)) return 40;
-  if (ensure(c, c->simp_keep, T * 4)) return 40;
-  if (ensure(c, c->simp_keep_scan, T * 4)) return 40;
-  if (ensure(c, c->simp_park, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_first, (L + 1) * 4)) return 40;
-  if (ensure(c, c->simp_troff_final, (L + 1) * 4)) return 40;
-  if (ensure(c, c->simp_deg, V * 4)) return 40;
-  if (ensure(c, c->simp_adj, V * 4)) return 40;
-  if (ensure(c, c->simp_accept, V * 4)) return 40;
-  // proposal-acceptance second matching wave (contract knob shared
-  // with the oracle; MG_SIMP_PROPOSE=0 disables on both sides)
-  uint32_t propose = 1;
-  {
-    const char *e = getenv("MG_SIMP_PROPOSE");
-    if (e && e[0] == '0') propose = 0;
-  }
-
-  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
-  float *verts = (float *)c->verts.ptr;
-
-  // faces -> global vertex ids, label per face
-  {
-    uint64_t nbt = (T + blk - 1) / blk;
-    hipLaunchKernelGGL(k_globalize_faces, dim3((uint32_t)nbt), dim3(blk), 0,
-                       s, faces_g, lab_sorted,
-                       (const uint32_t *)c->vbase.ptr,
-                       (uint32_t *)c->simp_flab.ptr, T);
-    uint32_t nbl = (uint32_t)((L + 255) / 256);
-    hipLaunchKernelGGL(k_init_simplify, dim3(nbl), dim3(256), 0, s,
-                       (const uint32_t *)c->tri_off.ptr, nt_cur, target,
-                       active, reduction_factor, (uint32_t)L);
-  }
-  HIP_TRY(c, hipGetLastError(), 40);
-
-  // labels up to SIMP_BIG_CAP faces simplify entirely inside one
-  // workgroup each (cache-resident round loop, no global sorts); only
-  // bigger labels go through the global-rounds machinery below.
-  const uint32_t SIMP_BIG_CAP = 65536;
-  // sub-rounds per quadric recompute (contract constant; the oracle
-  // reads the same env knob, default 6 on both sides)
-  uint32_t simp_subs = 6;
-  {
-    const char *e = getenv("MG_SIMP_SUBS");
-    if (e && e[0]) { int v = atoi(e); simp_subs = v < 1 ? 1u : (uint32_t)v; }
-  }
-  if (getenv("MG_SIMP_PROF"))
-    HIP_TRY(c, hipMemsetAsync((unsigned long long *)c->lh_misc.ptr + 8, 0,
-                              48, s), 40);
-  // round-count histogram (MG_SIMP_ROUNDHIST=1): groups/subs per label
-  uint32_t *d_rh = nullptr;
-  if (getenv("MG_SIMP_ROUNDHIST")) {
-    if (ensure(c, c->simp_rh, 176 * 4)) return 40;
-    d_rh = (uint32_t *)c->simp_rh.ptr;
-    HIP_TRY(c, hipMemsetAsync(d_rh, 0, 176 * 4, s), 40);
-  }
-  // biggest-label-first dispatch order (MG_SIMP_SCHED=1 enables;
-  // measured 8% WORSE on the 512^3/50k config: the front-loaded big
-  // labels all run the global-array fallback path and thrash when
-  // concentrated, and no straggler tail exists to begin with — per-label
-  // cycle histogram shows max 5.7 ms vs 61 ms wall)
-  uint32_t *d_sched = nullptr;
-  {
-    const char *e = getenv("MG_SIMP_SCHED");
-    if (e && e[0] == '1') {
-      if (ensure(c, c->simp_sched, 3 * L * 4)) return 40;
-      uint32_t *iota = (uint32_t *)c->simp_sched.ptr;
-      uint32_t *keys_out = iota + L;
-      d_sched = keys_out + L;
-      uint32_t nbl = (uint32_t)((L + 255) / 256);
-      hipLaunchKernelGGL(k_iota, dim3(nbl), dim3(256), 0, s, iota, L);
-      size_t tmp = 0;
-      hipError_t err = rocprim::radix_sort_pairs_desc(
-          nullptr, tmp, nt_cur, keys_out, iota, d_sched, L, 0u, 32u, s);
-      if (err != hipSuccess) { SET_ERR(c, "sched sort size"); return 40; }
-      if (ensure(c, c->sort_tmp, tmp)) return 40;
-      err = rocprim::radix_sort_pairs_desc(
-          c->sort_tmp.ptr, tmp, nt_cur, keys_out, iota, d_sched, L, 0u,
-          32u, s);
-      if (err != hipSuccess) { SET_ERR(c, "sched sort"); return 40; }
-    }
-  }
-  {
-    // default OFF since sub-round groups: the +24 KB LDS CSR payload
-    // costs blocks/CU and the recompute phases it serves are now ~25%
-    const char *clenv = getenv("MG_SIMP_CLLDS");  // "1" enables
-    const bool use_cl = (clenv && clenv[0] == '1');
-    // block size: 256 default; MG_SIMP_BS in {128,256,512} for A/B
-    int bs = 256;
-    {
-      const char *e = getenv("MG_SIMP_BS");
-      if (e && e[0]) { int v = atoi(e); if (v==128||v==256||v==512) bs = v; }
-    }
-    decltype(&k_simplify_label<false, 256, 2048>) ksl;
-    if (bs == 128)
-      ksl = use_cl ? k_simplify_label<true, 128, 2048>
-                   : k_simplify_label<false, 128, 2048>;
-    else if (bs == 512)
-      ksl = use_cl ? k_simplify_label<true, 512, 2048>
-                   : k_simplify_label<false, 512, 2048>;
-    else
-      ksl = use_cl ? k_simplify_label<true, 256, 2048>
-                   : k_simplify_label<false, 256, 2048>;
-    // single-wave small-LDS variant takes labels with nv <= small_cap
-    // (~8.3 KB LDS -> ~19 blocks/CU, intra-wave barriers); the default
-    // variant takes the rest. Measured ~1% WORSE in-box (the serialized
-    // second launch eats the occupancy gain) -> default off;
-    // MG_SIMP_SMALL=1 enables for experiments.
-    const char *sm = getenv("MG_SIMP_SMALL");
-    const uint32_t small_cap = (sm && sm[0] == '1') ? 512u : 0u;
-    auto launch_band = [&](auto fn, hipStream_t st, int bsz,
-                           uint32_t nv_lo, uint32_t nv_hi,
-                           uint32_t nt_lo = 0u,
-                           uint32_t nt_hi = 0xFFFFFFFFu) {
-      hipLaunchKernelGGL(fn, dim3((uint32_t)L), dim3(bsz), 0, st,
-                         faces_g, (uint32_t *)c->simp_faces_alt.ptr,
-                         (const uint32_t *)c->tri_off.ptr,
-                         (const uint32_t *)c->vbase.ptr,
-                         verts, (float *)c->simp_Q.ptr,
-                         (unsigned long long *)c->simp_pick.ptr,
-                         (uint32_t *)c->simp_remap.ptr,
-                         (uint32_t *)c->simp_deg.ptr,
-                         (uint32_t *)c->simp_adj.ptr,
-                         (uint32_t *)c->simp_pk.ptr,
-                         (SimpPlane *)c->simp_fq.ptr,
-                         (uint8_t *)c->simp_valid.ptr,
-                         nt_cur, target, active,
-                         (uint32_t *)c->simp_park.ptr,
-                         getenv("MG_SIMP_PROF")
-                             ? (unsigned long long *)c->lh_misc.ptr + 8
-                             : nullptr,
-                         d_rh,
-                         max_cost, (uint32_t)L, SIMP_BIG_CAP, simp_subs,
-                         nv_lo, nv_hi, nt_lo, nt_hi,
-                         (uint32_t *)c->simp_accept.ptr,
-                         propose, d_sched);
-    };
-    if (small_cap)
-      launch_band(k_simplify_label<false, 64, 512>, s, 64, 0u, small_cap);
-    // nv-banded dispatch (MG_SIMP_BANDS=0 disables): labels with
-    // 2048 < nv <= 4096 get their own CAPV=4096 instantiation (64 KB
-    // LDS, 2 blocks/CU) on a SECOND stream, concurrent with the main
-    // band — previously they fell into the global-array mode whose
-    // hot per-vertex atomics serialize on L2 lines
-    const char *bandsenv = getenv("MG_SIMP_BANDS");
-    const bool bands = !(bandsenv && bandsenv[0] == '0') && !use_cl;
-    if (bands) {
-      // record BEFORE enqueuing band A: stream2 must wait only for the
-      // shared setup, so the other bands run CONCURRENT with A
-      // (recording after A serialized them — 51 ms vs 38 ms overlapped)
-      HIP_TRY(c, hipEventRecord(c->ev[9], s), 40);
-      HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[9], 0), 40);
-      // WAVEMODE band (MG_SIMP_WAVE=1 enables; default OFF — measured
-      // 19% WORSE on 512^3/50k: 7 labels/CU resident vs 3, but one
-      // 64-lane wave pays 4x the per-pass iterations and its in-flight
-      // load window can't cover the longer chains): one wave per label
-      // for the small-label mass (nt<=8192, nv<=2048), 20 KB LDS/label
-      const char *wenv = getenv("MG_SIMP_WAVE");
-      const bool wave = (wenv && wenv[0] == '1');
-      if (wave) {
-        launch_band(k_simplify_label<false, 64, 2048, true>, s, 64,
-                    small_cap, 2048u, 0u, 8192u);
-        launch_band(ksl, c->stream2, bs, small_cap, 2048u,
-                    8192u, 0xFFFFFFFFu);
-      } else {
-        launch_band(ksl, s, bs, small_cap, 2048u);
-      }
-      launch_band(k_simplify_label<false, 256, 4096>, c->stream2, 256,
-                  2048u, 4096u);
-      launch_band(ksl, c->stream2, bs, 4096u, 0xFFFFFFFFu);
-      HIP_TRY(c, hipEventRecord(c->ev[10], c->stream2), 40);
-      HIP_TRY(c, hipStreamWaitEvent(s, c->ev[10], 0), 40);
-    } else {
-      launch_band(ksl, s, bs, small_cap, 0xFFFFFFFFu);
-    }
-    HIP_TRY(c, hipGetLastError(), 40);
-    if (getenv("MG_SIMP_PROF")) {
-      unsigned long long hp[6];
-      HIP_TRY(c, hipMemcpyAsync(hp, (unsigned long long *)c->lh_misc.ptr + 8,
-                                48, hipMemcpyDeviceToHost, s), 40);
-      HIP_TRY(c, hipStreamSynchronize(s), 40);
-      const char *nm[6] = {"loophead", "planes+deg", "scan+fill",
-                           "sortaccum", "picks", "collapse+compact"};
-      fprintf(stderr, "[mg simp phases, summed tid0 cycles]");
-      for (int k = 0; k < 6; ++k)
-        fprintf(stderr, " %s=%llu", nm[k], hp[k]);
-      fprintf(stderr, "\n");
-    }
-    if (d_rh) {
-      uint32_t h[176];
-      HIP_TRY(c, hipMemcpyAsync(h, d_rh, 176 * 4, hipMemcpyDeviceToHost, s),
-              40);
-      HIP_TRY(c, hipStreamSynchronize(s), 40);
-      fprintf(stderr, "[mg simp rounds] labels=%u sum_groups=%u "
-              "sum_subs=%u sum_nt0=%u max_cycles=%u (nt0=%u)\n",
-              h[130], h[128], h[129], h[131], h[132], h[133]);
-      {
-        unsigned long long lds_c, glob_c;
-        memcpy(&lds_c, &h[160], 8); memcpy(&glob_c, &h[162], 8);
-        fprintf(stderr, "[mg simp mode split] lds: n=%u cyc=%llu | "
-                "global: n=%u cyc=%llu\n", h[164], lds_c, h[165], glob_c);
-      }
-      fprintf(stderr, "[mg simp log2-cycle hist]");
-      for (int k = 0; k < 26; ++k)
-        if (h[134 + k]) fprintf(stderr, " %d:%u", k, h[134 + k]);
-      fprintf(stderr, "\n");
-      fprintf(stderr, "[mg simp group hist]");
-      for (int k = 0; k < 64; ++k)
-        if (h[k]) fprintf(stderr, " %d:%u", k, h[k]);
-      fprintf(stderr, "\n[mg simp subs hist]");
-      for (int k = 0; k < 64; ++k)
-        if (h[64 + k]) fprintf(stderr, " %d:%u", k, h[64 + k]);
-      fprintf(stderr, "\n");
-    }
-  }
-  // drop the per-label-kernel labels from the working set; park big
-  // never-active labels (their final faces are their originals)
-  {
-    uint64_t nbt2 = (T + blk - 1) / blk;
-    uint32_t *flab2 = (uint32_t *)c->simp_flab.ptr;
-    hipLaunchKernelGGL(k_flag_active_faces, dim3((uint32_t)nbt2), dim3(blk),
-                       0, s, flab2, active, (uint32_t *)c->simp_keep.ptr, T);
-    size_t tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(
-        nullptr, tmp, (uint32_t *)c->simp_keep.ptr,
-        (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "prepark scan size"); return 50; }
-    if (ensure(c, c->scan_tmp, tmp)) return 50;
-    e = rocprim::exclusive_scan(
-        c->scan_tmp.ptr, tmp, (uint32_t *)c->simp_keep.ptr,
-        (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "prepark scan"); return 50; }
-    hipLaunchKernelGGL(k_first_label_idx, dim3((uint32_t)nbt2), dim3(blk),
-                       0, s, flab2, (uint32_t *)c->simp_first.ptr, T);
-    hipLaunchKernelGGL(k_park_scatter, dim3((uint32_t)nbt2), dim3(blk), 0,
-                       s, faces_g, flab2,
-                       (const uint32_t *)c->simp_keep.ptr,
-                       (const uint32_t *)c->simp_keep_scan.ptr,
-                       (const uint32_t *)c->simp_first.ptr,
-                       (const uint32_t *)c->tri_off.ptr,
-                       (uint32_t *)c->simp_faces_alt.ptr,
-                       (uint32_t *)c->simp_flab_alt.ptr,
-                       (uint32_t *)c->simp_park.ptr, SIMP_BIG_CAP, T);
-    hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                       (const uint32_t *)c->simp_keep_scan.ptr,
-                       (const uint32_t *)c->simp_keep.ptr, T,
-                       (uint32_t *)c->lh_misc.ptr + 4);
-    uint32_t act_total = 0;
-    HIP_TRY(c, hipMemcpyAsync(&act_total, (uint32_t *)c->lh_misc.ptr + 4,
-                              4, hipMemcpyDeviceToHost, s), 50);
-    HIP_TRY(c, hipStreamSynchronize(s), 50);
-    std::swap(c->faces, c->simp_faces_alt);
-    std::swap(c->simp_flab, c->simp_flab_alt);
-    faces_g = (uint32_t *)c->faces.ptr;
-    T = act_total;
-  }
-
-  bool simp_done = false;
-  for (int group = 0; group < 65536 && !simp_done; ++group) {
-    // any label still active?
-    HIP_TRY(c, hipMemsetAsync(d_any, 0, 4, s), 41);
-    {
-      uint32_t nbl = (uint32_t)((L + 255) / 256);
-      hipLaunchKernelGGL(k_any_active, dim3(nbl), dim3(256), 0, s,
-                         active, (uint32_t)L, d_any);
-    }
-    uint32_t any = 0;
-    HIP_TRY(c, hipMemcpyAsync(&any, d_any, 4, hipMemcpyDeviceToHost, s), 41);
-    HIP_TRY(c, hipStreamSynchronize(s), 41);
-    if (!any) break;
-
-    uint64_t nbt = (T + blk - 1) / blk;
-    uint64_t NP = 3 * T;
-    uint64_t nbp = (NP + blk - 1) / blk;
-    uint32_t *flab = (uint32_t *)c->simp_flab.ptr;
-
-    hipLaunchKernelGGL(k_face_planes, dim3((uint32_t)nbt), dim3(blk), 0, s,
-                       faces_g, verts, active, flab,
-                       (SimpPlane *)c->simp_fq.ptr,
-                       (uint8_t *)c->simp_valid.ptr, T);
-    hipLaunchKernelGGL(k_emit_vf_pairs, dim3((uint32_t)nbt), dim3(blk), 0, s,
-                       faces_g, active, flab,
-                       (uint32_t *)c->simp_pk.ptr,
-                       (uint32_t *)c->simp_pv.ptr, T);
-    // stable sort pairs by vertex (face order preserved within vertex)
-    {
-      rocprim::double_buffer<uint32_t> dk((uint32_t *)c->simp_pk.ptr,
-                                          (uint32_t *)c->simp_pk_alt.ptr);
-      rocprim::double_buffer<uint32_t> dv((uint32_t *)c->simp_pv.ptr,
-                                          (uint32_t *)c->simp_pv_alt.ptr);
-      size_t tmp = 0;
-      hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, dk, dv, NP,
-                                               0u, 32u, s);
-      if (e != hipSuccess) { SET_ERR(c, "simplify sort size query"); return 42; }
-      if (ensure(c, c->sort_tmp, tmp)) return 42;
-      e = rocprim::radix_sort_pairs(c->sort_tmp.ptr, tmp, dk, dv, NP,
-                                    0u, 32u, s);
-      if (e != hipSuccess) { SET_ERR(c, "simplify sort"); return 42; }
-      hipLaunchKernelGGL(k_accum_quadrics, dim3((uint32_t)nbp), dim3(blk), 0,
-                         s, dk.current(), dv.current(),
-                         (const SimpPlane *)c->simp_fq.ptr,
-                         (const uint8_t *)c->simp_valid.ptr,
-                         (float *)c->simp_Q.ptr, NP);
-    }
-    // sub-rounds: reuse the group's quadrics with GH merging (the same
-    // group structure as the per-label kernel and the oracle). Measured
-    // on 512^3/200 big labels: subs>1 is ~5% SLOWER here (the T- and
-    // V-sized sub passes dwarf the recompute they skip, unlike the
-    // per-label kernel) -> the contract pins big labels at 1 sub/group.
-    const uint32_t subs_global = 1;
-    for (uint32_t sub = 0; sub < subs_global; ++sub) {
-    uint64_t nbs = (T + blk - 1) / blk;  // T shrinks between subs
-    HIP_TRY(c, hipMemsetAsync(c->simp_pick.ptr, 0xFF, V * 8, s), 43);
-    if (propose)
-      HIP_TRY(c, hipMemsetAsync(c->simp_accept.ptr, 0xFF, V * 4, s), 43);
-    hipLaunchKernelGGL(k_edge_pick, dim3((uint32_t)nbs), dim3(blk), 0, s,
-                       faces_g, active, flab,
-                       (const uint32_t *)c->vbase.ptr, verts,
-                       (const float *)c->simp_Q.ptr,
-                       (unsigned long long *)c->simp_pick.ptr, max_cost, T);
-    if (group == 0 && sub == 0 && getenv("MG_DEBUG_SIMPLIFY")) {
-      float hq[40]; unsigned long long hp[8]; uint32_t hf[12];
-      (void)hipMemcpyAsync(hq, c->simp_Q.ptr, sizeof(hq), hipMemcpyDeviceToHost, s);
-      (void)hipMemcpyAsync(hp, c->simp_pick.ptr, sizeof(hp), hipMemcpyDeviceToHost, s);
-      (void)hipMemcpyAsync(hf, faces_g, sizeof(hf), hipMemcpyDeviceToHost, s);
-      (void)hipStreamSynchronize(s);
-      fprintf(stderr, "[mg] faces0-3:");
-      for (int k = 0; k < 12; ++k) fprintf(stderr, " %u", hf[k]);
-      fprintf(stderr, "\n[mg] Q0: ");
-      for (int k = 0; k < 10; ++k) fprintf(stderr, "%a ", hq[k]);
-      fprintf(stderr, "\n[mg] Q1: ");
-      for (int k = 10; k < 20; ++k) fprintf(stderr, "%a ", hq[k]);
-      fprintf(stderr, "\n[mg] pick0-7:");
-      for (int k = 0; k < 8; ++k) fprintf(stderr, " %llx", hp[k]);
-      fprintf(stderr, "\n");
-    }
-    {
-      uint64_t nbv = (V + blk - 1) / blk;
-      hipLaunchKernelGGL(k_iota, dim3((uint32_t)nbv), dim3(blk), 0, s,
-                         (uint32_t *)c->simp_remap.ptr, V);
-      hipLaunchKernelGGL(k_collapse, dim3((uint32_t)nbv), dim3(blk), 0, s,
-                         (unsigned long long *)c->simp_pick.ptr, verts,
-                         (uint32_t *)c->simp_remap.ptr,
-                         (float *)c->simp_Q.ptr, V);
-      if (propose) {
-        hipLaunchKernelGGL(k_propose, dim3((uint32_t)nbv), dim3(blk), 0, s,
-                           (const unsigned long long *)c->simp_pick.ptr,
-                           (uint32_t *)c->simp_accept.ptr, V);
-        hipLaunchKernelGGL(k_accept, dim3((uint32_t)nbv), dim3(blk), 0, s,
-                           (const unsigned long long *)c->simp_pick.ptr,
-                           (const uint32_t *)c->simp_accept.ptr,
-                           verts, (uint32_t *)c->simp_remap.ptr,
-                           (float *)c->simp_Q.ptr, V);
-      }
-    }
-    hipLaunchKernelGGL(k_remap_faces, dim3((uint32_t)nbs), dim3(blk), 0, s,
-                       faces_g, (const uint32_t *)c->simp_remap.ptr,
-                       (uint32_t *)c->simp_keep.ptr, T);
-    {
-      size_t tmp = 0;
-      hipError_t e = rocprim::exclusive_scan(
-          nullptr, tmp, (uint32_t *)c->simp_keep.ptr,
-          (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-          rocprim::plus<uint32_t>(), s);
-      if (e != hipSuccess) { SET_ERR(c, "keep scan size query"); return 44; }
-      if (ensure(c, c->scan_tmp, tmp)) return 44;
-      e = rocprim::exclusive_scan(
-          c->scan_tmp.ptr, tmp, (uint32_t *)c->simp_keep.ptr,
-          (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-          rocprim::plus<uint32_t>(), s);
-      if (e != hipSuccess) { SET_ERR(c, "keep scan"); return 44; }
-    }
-    hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                       (const uint32_t *)c->simp_keep_scan.ptr,
-                       (const uint32_t *)c->simp_keep.ptr, T,
-                       (uint32_t *)c->lh_misc.ptr + 4);
-    uint32_t kept = 0;
-    HIP_TRY(c, hipMemcpyAsync(&kept, (uint32_t *)c->lh_misc.ptr + 4, 4,
-                              hipMemcpyDeviceToHost, s), 44);
-    HIP_TRY(c, hipMemsetAsync(nt_new, 0, L * 4, s), 44);
-    hipLaunchKernelGGL(k_compact_faces, dim3((uint32_t)nbs), dim3(blk), 0, s,
-                       faces_g, flab, (const uint32_t *)c->simp_keep.ptr,
-                       (const uint32_t *)c->simp_keep_scan.ptr,
-                       (uint32_t *)c->simp_faces_alt.ptr,
-                       (uint32_t *)c->simp_flab_alt.ptr, nt_new, T);
-    {
-      uint32_t nbl = (uint32_t)((L + 255) / 256);
-      hipLaunchKernelGGL(k_update_active, dim3(nbl), dim3(256), 0, s,
-                         nt_new, nt_cur, target, active, d_any, (uint32_t)L,
-                         sub == 0 ? 1u : 0u);
-    }
-    HIP_TRY(c, hipGetLastError(), 44);
-    HIP_TRY(c, hipStreamSynchronize(s), 44);
-    std::swap(c->faces, c->simp_faces_alt);
-    std::swap(c->simp_flab, c->simp_flab_alt);
-    faces_g = (uint32_t *)c->faces.ptr;
-    T = kept;
-    if (T == 0) { simp_done = true; break; }
-
-    // park faces of labels that just went inactive: working set keeps
-    // only active labels (late rounds touch only the active tail)
-    {
-      uint64_t nbt2 = (T + blk - 1) / blk;
-      uint32_t *flab2 = (uint32_t *)c->simp_flab.ptr;
-      hipLaunchKernelGGL(k_flag_active_faces, dim3((uint32_t)nbt2),
-                         dim3(blk), 0, s, flab2, active,
-                         (uint32_t *)c->simp_keep.ptr, T);
-      size_t tmp = 0;
-      hipError_t e = rocprim::exclusive_scan(
-          nullptr, tmp, (uint32_t *)c->simp_keep.ptr,
-          (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-          rocprim::plus<uint32_t>(), s);
-      if (e != hipSuccess) { SET_ERR(c, "park scan size query"); return 47; }
-      if (ensure(c, c->scan_tmp, tmp)) return 47;
-      e = rocprim::exclusive_scan(
-          c->scan_tmp.ptr, tmp, (uint32_t *)c->simp_keep.ptr,
-          (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-          rocprim::plus<uint32_t>(), s);
-      if (e != hipSuccess) { SET_ERR(c, "park scan"); return 47; }
-      hipLaunchKernelGGL(k_first_label_idx, dim3((uint32_t)nbt2), dim3(blk),
-                         0, s, flab2, (uint32_t *)c->simp_first.ptr, T);
-      hipLaunchKernelGGL(k_park_scatter, dim3((uint32_t)nbt2), dim3(blk), 0,
-                         s, faces_g, flab2,
-                         (const uint32_t *)c->simp_keep.ptr,
-                         (const uint32_t *)c->simp_keep_scan.ptr,
-                         (const uint32_t *)c->simp_first.ptr,
-                         (const uint32_t *)c->tri_off.ptr,
-                         (uint32_t *)c->simp_faces_alt.ptr,
-                         (uint32_t *)c->simp_flab_alt.ptr,
-                         (uint32_t *)c->simp_park.ptr, SIMP_BIG_CAP, T);
-      hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                         (const uint32_t *)c->simp_keep_scan.ptr,
-                         (const uint32_t *)c->simp_keep.ptr, T,
-                         (uint32_t *)c->lh_misc.ptr + 4);
-      uint32_t act_total = 0;
-      HIP_TRY(c, hipMemcpyAsync(&act_total, (uint32_t *)c->lh_misc.ptr + 4,
-                                4, hipMemcpyDeviceToHost, s), 47);
-      HIP_TRY(c, hipStreamSynchronize(s), 47);
-      std::swap(c->faces, c->simp_faces_alt);
-      std::swap(c->simp_flab, c->simp_flab_alt);
-      faces_g = (uint32_t *)c->faces.ptr;
-      T = act_total;
-      if (T == 0) break;
-    }
-    }  // sub loop
-  }
-
-  // any faces still in the working set (round-cap exit): force-park them
-  if (T > 0) {
-    HIP_TRY(c, hipMemsetAsync(active, 0, L, s), 48);
-    uint64_t nbt2 = (T + blk - 1) / blk;
-    uint32_t *flab2 = (uint32_t *)c->simp_flab.ptr;
-    hipLaunchKernelGGL(k_flag_active_faces, dim3((uint32_t)nbt2), dim3(blk),
-                       0, s, flab2, active, (uint32_t *)c->simp_keep.ptr, T);
-    size_t tmp = 0;
-    rocprim::exclusive_scan(nullptr, tmp, (uint32_t *)c->simp_keep.ptr,
-                            (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-                            rocprim::plus<uint32_t>(), s);
-    if (ensure(c, c->scan_tmp, tmp)) return 48;
-    rocprim::exclusive_scan(c->scan_tmp.ptr, tmp,
-                            (uint32_t *)c->simp_keep.ptr,
-                            (uint32_t *)c->simp_keep_scan.ptr, 0u, T,
-                            rocprim::plus<uint32_t>(), s);
-    hipLaunchKernelGGL(k_first_label_idx, dim3((uint32_t)nbt2), dim3(blk),
-                       0, s, flab2, (uint32_t *)c->simp_first.ptr, T);
-    hipLaunchKernelGGL(k_park_scatter, dim3((uint32_t)nbt2), dim3(blk), 0,
-                       s, faces_g, flab2,
-                       (const uint32_t *)c->simp_keep.ptr,
-                       (const uint32_t *)c->simp_keep_scan.ptr,
-                       (const uint32_t *)c->simp_first.ptr,
-                       (const uint32_t *)c->tri_off.ptr,
-                       (uint32_t *)c->simp_faces_alt.ptr,
-                       (uint32_t *)c->simp_flab_alt.ptr,
-                       (uint32_t *)c->simp_park.ptr, SIMP_BIG_CAP, T);
-    HIP_TRY(c, hipGetLastError(), 48);
-  }
-
-  // final face array: per-label slices from the park store, lid order
-  {
-    size_t tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(
-        nullptr, tmp, nt_cur, (uint32_t *)c->simp_troff_final.ptr, 0u, L,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "final troff scan size"); return 49; }
-    if (ensure(c, c->scan_tmp, tmp)) return 49;
-    e = rocprim::exclusive_scan(
-        c->scan_tmp.ptr, tmp, nt_cur, (uint32_t *)c->simp_troff_final.ptr,
-        0u, L, rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "final troff scan"); return 49; }
-    hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                       (const uint32_t *)c->simp_troff_final.ptr, nt_cur, L,
-                       (uint32_t *)c->lh_misc.ptr + 6);
-    HIP_TRY(c, hipMemcpyAsync((uint32_t *)c->simp_troff_final.ptr + L,
-                              (uint32_t *)c->lh_misc.ptr + 6, 4,
-                              hipMemcpyDeviceToDevice, s), 49);
-    uint32_t final_total = 0;
-    HIP_TRY(c, hipMemcpyAsync(&final_total, (uint32_t *)c->lh_misc.ptr + 6,
-                              4, hipMemcpyDeviceToHost, s), 49);
-    HIP_TRY(c, hipStreamSynchronize(s), 49);
-    T = final_total;
-    if (T > 0) {
-      uint64_t nbt2 = (T + blk - 1) / blk;
-      hipLaunchKernelGGL(k_gather_final, dim3((uint32_t)nbt2), dim3(blk), 0,
-                         s, (const uint32_t *)c->simp_park.ptr,
-                         (const uint32_t *)c->tri_off.ptr,
-                         (const uint32_t *)c->simp_troff_final.ptr,
-                         (uint32_t *)c->faces.ptr,
-                         (uint32_t *)c->simp_flab.ptr, (uint32_t)L, T);
-    }
-    faces_g = (uint32_t *)c->faces.ptr;
-    std::swap(c->tri_off, c->simp_troff_final);
-  }
-
-  // final: drop unreferenced vertices (stable), re-localize faces
-  if (ensure(c, c->simp_ref, (V + 1) * 4)) return 45;
-  if (ensure(c, c->simp_verts_alt, V * 12 + 12)) return 45;
-  if (ensure(c, c->simp_vbase_alt, (L + 1) * 4)) return 45;
-  uint32_t *ref = (uint32_t *)c->simp_ref.ptr;
-  uint32_t *newid = (uint32_t *)c->vtx_scan.ptr;  // NC*4 >= V*4, free now
-  HIP_TRY(c, hipMemsetAsync(ref, 0, V * 4, s), 45);
-  uint64_t NCk = 3 * T;
-  if (T > 0) {
-    uint64_t nbc = (NCk + blk - 1) / blk;
-    hipLaunchKernelGGL(k_mark_ref, dim3((uint32_t)nbc), dim3(blk), 0, s,
-                       faces_g, ref, NCk);
-  }
-  {
-    size_t tmp = 0;
-    hipError_t e = rocprim::exclusive_scan(
-        nullptr, tmp, ref, newid, 0u, V, rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "ref scan size query"); return 45; }
-    if (ensure(c, c->scan_tmp, tmp)) return 45;
-    e = rocprim::exclusive_scan(
-        c->scan_tmp.ptr, tmp, ref, newid, 0u, V,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "ref scan"); return 45; }
-  }
-  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, newid, ref, V,
-                     (uint32_t *)c->lh_misc.ptr + 5);
-  uint32_t newV = 0;
-  HIP_TRY(c, hipMemcpyAsync(&newV, (uint32_t *)c->lh_misc.ptr + 5, 4,
-                            hipMemcpyDeviceToHost, s), 45);
-  HIP_TRY(c, hipStreamSynchronize(s), 45);
-  {
-    uint64_t nbv = (V + blk - 1) / blk;
-    hipLaunchKernelGGL(k_scatter_verts, dim3((uint32_t)nbv), dim3(blk), 0, s,
-                       verts, ref, newid, (float *)c->simp_verts_alt.ptr, V);
-    uint32_t nbl = (uint32_t)((L + 2 + 255) / 256);
-    hipLaunchKernelGGL(k_new_vbase, dim3(nbl), dim3(256), 0, s,
-                       (const uint32_t *)c->vbase.ptr, newid,
-                       (uint32_t *)c->simp_vbase_alt.ptr, (uint32_t)L, newV);
-    if (T > 0) {
-      uint64_t nbt = (T + blk - 1) / blk;
-      hipLaunchKernelGGL(k_localize_faces, dim3((uint32_t)nbt), dim3(blk), 0,
-                         s, faces_g, newid,
-                         (const uint32_t *)c->simp_flab.ptr,
-                         (const uint32_t *)c->simp_vbase_alt.ptr,
-                         (uint32_t *)c->simp_faces_alt.ptr, T);
-    }
-  }
-  HIP_TRY(c, hipGetLastError(), 46);
-  std::swap(c->faces, c->simp_faces_alt);
-  std::swap(c->verts, c->simp_verts_alt);
-  std::swap(c->vbase, c->simp_vbase_alt);
-  *p_T = T;
-  *p_V = newV;
-  return 0;
-}
-
-static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
-                           int sx, int sy, int sz, int dtype,
-                           float rx, float ry, float rz,
-                           uint32_t reduction_factor, float max_error,
-                           int voxel_centered, uint64_t dust_threshold,
-                           uint32_t flags_, const mg_label_map *map,
-                           uint32_t fill_level, mg_meshset **out) {
-  const size_t esize = (dtype == MG_U64) ? 8 : 4;
-  const uint64_t nvox = (uint64_t)sx * sy * sz;
-  GridDims g;
-  g.sx = sx; g.sy = sy; g.sz = sz;
-  g.ncx = sx > 1 ? sx - 1 : 0;
-  g.ncy = sy > 1 ? sy - 1 : 0;
-  g.ncz = sz > 1 ? sz - 1 : 0;
-  g.nsegx = (g.ncx + WAVE - 1) / WAVE;
-  g.nseg = g.nsegx * g.ncy * g.ncz;
-
-  memset(&c->stats, 0, sizeof(c->stats));
-  c->stats.bytes_read_algorithmic = nvox * esize;
-
-  hipStream_t s = c->stream;
-
-  // trivial empty-cell-grid case
-  if (g.nseg == 0) {
-    mg_meshset *ms = (mg_meshset *)calloc(
-        1, sizeof(mg_meshset) + 2 * sizeof(void *));
-    *out = ms;
-    if (fill_level) {  // nothing to mesh in the hole volume either
-      c->holes_valid = true;
-      c->holes_sx = sx; c->holes_sy = sy; c->holes_sz = sz;
-      c->holes_dtype = dtype;
-    }
-    return 0;
-  }
-
-  HIP_TRY(c, hipEventRecord(c->ev[0], s), 10);
-
-  // H2D (skipped when the caller staged the identical volume already)
-  if ((flags_ & MG_FLAG_SKIP_H2D) && c->labels.cap >= nvox * esize) {
-    // resident input: nothing to upload
-  } else {
-    if (ensure(c, c->labels, nvox * esize)) return 11;
-    HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels_host, nvox * esize,
-                              hipMemcpyHostToDevice, s), 11);
-  }
-  HIP_TRY(c, hipEventRecord(c->ev[1], s), 11);
-
-  // device dust removal (three volume passes; see k_dust_* above)
-  if (dust_threshold > 0) {
-    const int dblk = 256;
-    const uint32_t dnb = 4096;
-    for (;;) {
-      if (ensure(c, c->lh_keys, c->lh_slots * 8)) return 16;
-      if (ensure(c, c->lh_vals, c->lh_slots * 4)) return 16;
-      if (ensure(c, c->lh_misc, 256)) return 16;
-      HIP_TRY(c, hipMemsetAsync(c->lh_keys.ptr, 0, c->lh_slots * 8, s), 16);
-      HIP_TRY(c, hipMemsetAsync(c->lh_misc.ptr, 0, 256, s), 16);
-      LabelHash dlh;
-      dlh.keys = (uint64_t *)c->lh_keys.ptr;
-      dlh.vals = (uint32_t *)c->lh_vals.ptr;
-      dlh.counter = (uint32_t *)c->lh_misc.ptr;
-      dlh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
-      dlh.nslots = c->lh_slots;
-      if (dtype == MG_U64)
-        hipLaunchKernelGGL(k_dust_build<uint64_t>, dim3(dnb), dim3(dblk),
-                           0, s, (const uint64_t *)c->labels.ptr, nvox, dlh);
-      else
-        hipLaunchKernelGGL(k_dust_build<uint32_t>, dim3(dnb), dim3(dblk),
-                           0, s, (const uint32_t *)c->labels.ptr, nvox, dlh);
-      uint32_t misc[2] = {0, 0};
-      HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8,
-                                hipMemcpyDeviceToHost, s), 16);
-      HIP_TRY(c, hipStreamSynchronize(s), 16);
-      if (misc[1]) {  // hash overflow: grow and retry
-        if (c->lh_slots >= (1ull << 27)) {
-          SET_ERR(c, "label hash overflow (dust) at %llu slots",
-                  (unsigned long long)c->lh_slots);
-          return 16;
-        }
-        c->lh_slots <<= 2;
-        continue;
-      }
-      uint32_t ndl = misc[0];
-      if (ndl == 0) break;
-      if (ensure(c, c->order, (uint64_t)ndl * 4)) return 16;
-      HIP_TRY(c, hipMemsetAsync(c->order.ptr, 0, (uint64_t)ndl * 4, s), 16);
-      if (dtype == MG_U64) {
-        hipLaunchKernelGGL(k_dust_count<uint64_t>, dim3(dnb), dim3(dblk),
-                           0, s, (const uint64_t *)c->labels.ptr, nvox,
-                           dlh, (uint32_t *)c->order.ptr);
-        hipLaunchKernelGGL(k_dust_zero<uint64_t>, dim3(dnb), dim3(dblk),
-                           0, s, (uint64_t *)c->labels.ptr, nvox, dlh,
-                           (const uint32_t *)c->order.ptr, dust_threshold);
-      } else {
-        hipLaunchKernelGGL(k_dust_count<uint32_t>, dim3(dnb), dim3(dblk),
-                           0, s, (const uint32_t *)c->labels.ptr, nvox,
-                           dlh, (uint32_t *)c->order.ptr);
-        hipLaunchKernelGGL(k_dust_zero<uint32_t>, dim3(dnb), dim3(dblk),
-                           0, s, (uint32_t *)c->labels.ptr, nvox, dlh,
-                           (const uint32_t *)c->order.ptr, dust_threshold);
-      }
-      HIP_TRY(c, hipGetLastError(), 16);
-      break;
-    }
-  }
-
-  // label map in place on the resident labels (after dust, which counted
-  // the RAW labels — the reference's order, mesh.py:193-204)
-  if (map) {
-    const uint64_t n = map->n;
-    MapTable mt;
-    mt.nslots = next_pow2_u64(std::max<uint64_t>(2 * n, 64));
-    if (ensure(c, c->map_tab, mt.nslots * 16)) return 41;
-    if (ensure(c, c->lh_misc, 256)) return 41;
-    mt.slots = (ulonglong2 *)c->map_tab.ptr;
-    uint32_t *d_err = (uint32_t *)c->lh_misc.ptr + 2;
-    HIP_TRY(c, hipEventRecord(c->ev[11], s), 41);
-    HIP_TRY(c, hipMemsetAsync(c->map_tab.ptr, 0, mt.nslots * 16, s), 41);
-    HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, s), 41);
-    if (n > 0) {
-      if (ensure(c, c->map_keys, n * 8)) return 41;
-      if (ensure(c, c->map_vals, n * 8)) return 41;
-      HIP_TRY(c, hipMemcpyAsync(c->map_keys.ptr, map->keys, n * 8,
-                                hipMemcpyHostToDevice, s), 41);
-      HIP_TRY(c, hipMemcpyAsync(c->map_vals.ptr, map->vals, n * 8,
-                                hipMemcpyHostToDevice, s), 41);
-      const int bblk = 256;
-      hipLaunchKernelGGL(k_map_build, dim3((uint32_t)((n + bblk - 1) / bblk)),
-                         dim3(bblk), 0, s, (const uint64_t *)c->map_keys.ptr,
-                         (const uint64_t *)c->map_vals.ptr, n, mt, d_err);
-    }
-    const uint64_t nvec = nvox / (16 / esize);
-    const uint32_t miss_zero = map->miss == MG_MAP_MISS_ZERO;
-    // MG_MAP_LDS=0 reverts small tables to the L2-probed kernel (A/B)
-    static const bool use_lds = []() {
-      const char *e = getenv("MG_MAP_LDS");
-      return !(e && e[0] == '0');
-    }();
-    if (use_lds && n <= MAP_LDS_MAX_ENTRIES) {
-      const int mblk = MAP_LDS_BLOCK;
-      const uint32_t mnb = (uint32_t)std::min<uint64_t>(
-          std::max<uint64_t>((nvec + mblk - 1) / mblk, 1), 512);
-      const size_t lds = mt.nslots * 16;  // <= 4096 slots = 64 KB
-      if (dtype == MG_U64)
-        hipLaunchKernelGGL(k_label_map_lds<uint64_t>, dim3(mnb), dim3(mblk),
-                           lds, s, (uint64_t *)c->labels.ptr, nvox, mt,
-                           miss_zero);
-      else
-        hipLaunchKernelGGL(k_label_map_lds<uint32_t>, dim3(mnb), dim3(mblk),
-                           lds, s, (uint32_t *)c->labels.ptr, nvox, mt,
-                           miss_zero);
-    } else {
-      const int mblk = 256;
-      const uint32_t mnb = (uint32_t)std::min<uint64_t>(
-          std::max<uint64_t>((nvec + mblk - 1) / mblk, 1), 4096);
-      if (dtype == MG_U64)
-        hipLaunchKernelGGL(k_label_map<uint64_t>, dim3(mnb), dim3(mblk), 0, s,
-                           (uint64_t *)c->labels.ptr, nvox, mt, miss_zero);
-      else
-        hipLaunchKernelGGL(k_label_map<uint32_t>, dim3(mnb), dim3(mblk), 0, s,
-                           (uint32_t *)c->labels.ptr, nvox, mt, miss_zero);
-    }
-    HIP_TRY(c, hipGetLastError(), 41);
-    HIP_TRY(c, hipEventRecord(c->ev[12], s), 41);
-    uint32_t map_err = 0;
-    HIP_TRY(c, hipMemcpyAsync(&map_err, d_err, 4, hipMemcpyDeviceToHost, s),
-            41);
-    HIP_TRY(c, hipStreamSynchronize(s), 41);
-    if (map_err & MAP_ERR_DUPLICATE) {
-      SET_ERR(c, "label map: duplicate key among %llu entries",
-              (unsigned long long)n);
-      return 42;
-    }
-    if (map_err) {
-      SET_ERR(c, "label map: table build failed (flag %u)", map_err);
-      return 42;
-    }
-    c->stats.ms_labelmap = ev_ms(c, 11, 12);
-  }
-
-  // fill_holes on the dusted + mapped labels (mesh.py:211-228): the
-  // resident volume becomes the filled one, the hole volume stays in
-  // c->holes for mg_mesh_holes
-  if (fill_level) {
-    HIP_TRY(c, hipEventRecord(c->ev[13], s), 56);
-    int frc = run_fill_holes(c, dtype, sx, sy, sz, fill_level, nullptr);
-    if (frc) return frc;
-    HIP_TRY(c, hipEventRecord(c->ev[14], s), 56);
-    c->holes_valid = true;
-    c->holes_sx = sx; c->holes_sy = sy; c->holes_sz = sz;
-    c->holes_dtype = dtype;
-  }
-
-  // label hash (grow-and-retry on overflow)
-  uint64_t total_tris = 0;
-  uint32_t nlabels = 0;
-  for (;;) {
-    if (ensure(c, c->lh_keys, c->lh_slots * 8)) return 12;
-    if (ensure(c, c->lh_vals, c->lh_slots * 4)) return 12;
-    if (ensure(c, c->lh_misc, 256)) return 12;
-    if (ensure(c, c->segcnt, g.nseg * 4)) return 12;
-    if (ensure(c, c->segoff, g.nseg * 4)) return 12;
-    HIP_TRY(c, hipMemsetAsync(c->lh_keys.ptr, 0, c->lh_slots * 8, s), 12);
-    HIP_TRY(c, hipMemsetAsync(c->lh_misc.ptr, 0, 256, s), 12);
-    LabelHash lh;
-    lh.keys = (uint64_t *)c->lh_keys.ptr;
-    lh.vals = (uint32_t *)c->lh_vals.ptr;
-    lh.counter = (uint32_t *)c->lh_misc.ptr;
-    lh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
-    lh.nslots = c->lh_slots;
-
-    int rc;
-    if (dtype == MG_U64)
-      rc = run_count_emit<uint64_t>(c, (const uint64_t *)c->labels.ptr, g, lh,
-                                    (uint32_t *)c->segcnt.ptr,
-                                    (uint32_t *)c->segoff.ptr,
-                                    &total_tris, &nlabels);
-    else
-      rc = run_count_emit<uint32_t>(c, (const uint32_t *)c->labels.ptr, g, lh,
-                                    (uint32_t *)c->segcnt.ptr,
-                                    (uint32_t *)c->segoff.ptr,
-                                    &total_tris, &nlabels);
-    if (rc == -100) {  // hash overflow: grow and retry
-      if (c->lh_slots >= (1ull << 27)) {
-        SET_ERR(c, "label hash overflow at %llu slots",
-                (unsigned long long)c->lh_slots);
-        return 13;
-      }
-      c->lh_slots <<= 2;
-      continue;
-    }
-    if (rc) return rc;
-    break;
-  }
-
-  LabelHash lh;
-  lh.keys = (uint64_t *)c->lh_keys.ptr;
-  lh.vals = (uint32_t *)c->lh_vals.ptr;
-  lh.counter = (uint32_t *)c->lh_misc.ptr;
-  lh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
-  lh.nslots = c->lh_slots;
-
-  c->stats.total_tris = total_tris;
-  c->stats.n_labels = nlabels;
-
-  if (total_tris == 0 || nlabels == 0) {
-    mg_meshset *ms = (mg_meshset *)calloc(
-        1, sizeof(mg_meshset) + 2 * sizeof(void *));
-    *out = ms;
-    HIP_TRY(c, hipStreamSynchronize(s), 14);
-    c->stats.ms_h2d = ev_ms(c, 0, 1);
-    if (fill_level) c->stats.ms_fill = ev_ms(c, 13, 14);
-    return 0;
-  }
-  if (total_tris > (1ull << 31) / 3 * 2) {  // 3T must fit u32 stream index
-    SET_ERR(c, "chunk produces %llu triangles (> corner-index limit); "
-            "split the task shape", (unsigned long long)total_tris);
-    return 15;
-  }
-  if (nlabels >= (1u << 27)) {  // label id shares the 64-bit weld key
-    SET_ERR(c, "%u labels exceed the 2^27 per-chunk label limit", nlabels);
-    return 15;
-  }
-
-  const uint64_t T = total_tris;
-  const uint64_t NC = 3 * T;  // corners
-
-  // label id -> value
-  if (ensure(c, c->label_values, (uint64_t)nlabels * 8)) return 17;
-  {
-    int blk = 256;
-    int64_t nb = (c->lh_slots + blk - 1) / blk;
-    hipLaunchKernelGGL(k_label_values, dim3((uint32_t)nb), dim3(blk), 0, s,
-                       lh, (uint64_t *)c->label_values.ptr, c->lh_slots);
-  }
-
-  // [3] emit
-  if (ensure(c, c->tri_label, T * 4)) return 18;
-  if (ensure(c, c->tri_keys, T * 8)) return 18;
-  {
-    int blk = 256;
-    int waves_per_blk = blk / WAVE;
-    int64_t nb = std::min<int64_t>((g.nseg + waves_per_blk - 1) / waves_per_blk,
-                                   8192);
-    nb = (nb + 7) & ~7ll;  // multiple of 8: XCD slab schedule coverage
-    if (dtype == MG_U64)
-      hipLaunchKernelGGL(k_emit<uint64_t>, dim3((uint32_t)nb), dim3(blk), 0, s,
-                         (const uint64_t *)c->labels.ptr, g,
-                         (const uint32_t *)c->segoff.ptr, lh,
-                         (uint32_t *)c->tri_label.ptr,
-                         (uint2 *)c->tri_keys.ptr);
-    else
-      hipLaunchKernelGGL(k_emit<uint32_t>, dim3((uint32_t)nb), dim3(blk), 0, s,
-                         (const uint32_t *)c->labels.ptr, g,
-                         (const uint32_t *)c->segoff.ptr, lh,
-                         (uint32_t *)c->tri_label.ptr,
-                         (uint2 *)c->tri_keys.ptr);
-  }
-  HIP_TRY(c, hipGetLastError(), 18);
-  HIP_TRY(c, hipEventRecord(c->ev[4], s), 18);
-
-  // [4] stable partition by label id. Default (MG_SORT_RECS=0 reverts):
-  // the 8-B records ride the radix sort as its 64-bit VALUES, so the
-  // weld insert reads them back SEQUENTIALLY instead of paying a
-  // random 8-B gather through the permutation.
-  const char *sre = getenv("MG_SORT_RECS");
-  const bool sort_recs = !(sre && sre[0] == '0');
-  if (ensure(c, c->keys_sorted, T * 20)) return 19;  // [sort-alt 8B] + [slot triples 12B]
-  if (ensure(c, c->tri_label_alt, T * 4)) return 19;
-  uint32_t *order_sorted = nullptr;
-  uint32_t *lab_sorted = nullptr;  // sort key output: label id per tri
-  const uint2 *rec_src = (const uint2 *)c->tri_keys.ptr;
-  uint32_t *slots_out = (uint32_t *)c->keys_sorted.ptr + 2 * T;
-  {
-    int blk = 256;
-    uint64_t nb = (T + blk - 1) / blk;
-    unsigned begin_bit = 0;
-    unsigned end_bit = 1;
-    while ((1u << end_bit) < nlabels) ++end_bit;
-    if (nlabels == 1) end_bit = 1;
-    rocprim::double_buffer<uint32_t> d_keys(
-        (uint32_t *)c->tri_label.ptr, (uint32_t *)c->tri_label_alt.ptr);
-    if (sort_recs) {
-      rocprim::double_buffer<uint64_t> d_vals(
-          (uint64_t *)c->tri_keys.ptr, (uint64_t *)c->keys_sorted.ptr);
-      size_t tmp_bytes = 0;
-      hipError_t e = rocprim::radix_sort_pairs(
-          nullptr, tmp_bytes, d_keys, d_vals, T, begin_bit, end_bit, s);
-      if (e != hipSuccess) { SET_ERR(c, "radix_sort size query failed"); return 19; }
-      if (ensure(c, c->sort_tmp, tmp_bytes)) return 19;
-      e = rocprim::radix_sort_pairs(
-          c->sort_tmp.ptr, tmp_bytes, d_keys, d_vals, T, begin_bit, end_bit, s);
-      if (e != hipSuccess) { SET_ERR(c, "radix_sort failed"); return 19; }
-      rec_src = (const uint2 *)d_vals.current();
-      order_sorted = nullptr;  // records already label-partitioned
-    } else {
-      if (ensure(c, c->order, T * 4)) return 19;
-      if (ensure(c, c->order_alt, T * 4)) return 19;
-      hipLaunchKernelGGL(k_iota, dim3((uint32_t)nb), dim3(blk), 0, s,
-                         (uint32_t *)c->order.ptr, T);
-      rocprim::double_buffer<uint32_t> d_vals(
-          (uint32_t *)c->order.ptr, (uint32_t *)c->order_alt.ptr);
-      size_t tmp_bytes = 0;
-      hipError_t e = rocprim::radix_sort_pairs(
-          nullptr, tmp_bytes, d_keys, d_vals, T, begin_bit, end_bit, s);
-      if (e != hipSuccess) { SET_ERR(c, "radix_sort size query failed"); return 19; }
-      if (ensure(c, c->sort_tmp, tmp_bytes)) return 19;
-      e = rocprim::radix_sort_pairs(
-          c->sort_tmp.ptr, tmp_bytes, d_keys, d_vals, T, begin_bit, end_bit, s);
-      if (e != hipSuccess) { SET_ERR(c, "radix_sort failed"); return 19; }
-      order_sorted = d_vals.current();
-    }
-    lab_sorted = d_keys.current();
-    // label ranges
-    if (ensure(c, c->tri_off, ((uint64_t)nlabels + 1) * 4)) return 19;
-    hipLaunchKernelGGL(k_label_ranges, dim3((uint32_t)nb), dim3(blk), 0, s,
-                       d_keys.current(), (uint32_t *)c->tri_off.ptr, T,
-                       nlabels);
-  }
-  HIP_TRY(c, hipGetLastError(), 19);
-  HIP_TRY(c, hipEventRecord(c->ev[5], s), 19);
-
-  // [5] weld — direct-addressed (edge, side) table, collision-free
-  const uint64_t wslots = 6 * nvox;  // 3 edges/voxel x 2 sides
-  if (wslots >= (1ull << 32)) {
-    SET_ERR(c, "chunk too large for the 32-bit weld table (%d x %d x %d); "
-            "split the task shape (the reference's own mesher bound is "
-            "1023x1023x511, igneous_cli/cli.py:1049-1052)", sx, sy, sz);
-    return 20;
-  }
-  uint64_t total_verts = 0;
-  if (ensure(c, c->wh_keys, wslots * 4)) return 20;   // wminp
-  if (ensure(c, c->vtx_scan, NC * 4)) return 20;
-  HIP_TRY(c, hipMemsetAsync(c->wh_keys.ptr, 0, wslots * 4, s), 20);
-  uint32_t *wminp = (uint32_t *)c->wh_keys.ptr;
-  // slot triples; the flag pass turns non-first entries into first positions
-  uint32_t *corner_ent = slots_out;
-  {
-    int blk = 256;
-    uint64_t nbt = (T + blk - 1) / blk;
-    int wi_cfg = 1;  // 0: 1024x1, 1: 1024x2, 2: 1024x4
-    if (const char *e = getenv("MG_WELD_INSERT_CFG")) wi_cfg = atoi(e);
-    uint32_t *rs_mut = slots_out;
-    const uint2 *tr = rec_src;
-    const int64_t sxy64 = g.sx * g.sy;
-    if (wi_cfg == 0) {
-      uint64_t nb2 = (T + 1023) / 1024;
-      hipLaunchKernelGGL((k_weld_insert<1024, 1>), dim3((uint32_t)nb2),
-                         dim3(1024), 0, s, tr, order_sorted, rs_mut, wminp,
-                         g.sx, sxy64, T);
-    } else if (wi_cfg == 1) {
-      uint64_t nb2 = (T + 2047) / 2048;
-      hipLaunchKernelGGL((k_weld_insert<1024, 2>), dim3((uint32_t)nb2),
-                         dim3(1024), 0, s, tr, order_sorted, rs_mut, wminp,
-                         g.sx, sxy64, T);
-    } else {
-      uint64_t nb2 = (T + 4095) / 4096;
-      hipLaunchKernelGGL((k_weld_insert<1024, 4>), dim3((uint32_t)nb2),
-                         dim3(1024), 0, s, tr, order_sorted, rs_mut, wminp,
-                         g.sx, sxy64, T);
-    }
-    // first-occurrence flags as a bit array + word-granular scan
-    const uint64_t nwords = (NC + 63) / 64;
-    unsigned long long *bits =
-        (unsigned long long *)c->vtx_scan.ptr;          // nwords * 8
-    uint32_t *wscan = (uint32_t *)c->vtx_scan.ptr + 2 * nwords;  // nwords * 4
-    // (vtx_scan buffer is NC*4 bytes >= nwords*12)
-    {
-      uint64_t nbw = (nwords * 64 + blk - 1) / blk;
-      hipLaunchKernelGGL(k_weld_flag_bits, dim3((uint32_t)nbw), dim3(blk),
-                         0, s, corner_ent, wminp, bits, NC, nwords);
-    }
-    auto it = rocprim::make_transform_iterator(bits, PopcWord{});
-    size_t tmp_bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(
-        nullptr, tmp_bytes, it, wscan, 0u, nwords,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "weld scan size query failed"); return 20; }
-    if (ensure(c, c->scan_tmp, tmp_bytes)) return 20;
-    e = rocprim::exclusive_scan(
-        c->scan_tmp.ptr, tmp_bytes, it, wscan, 0u, nwords,
-        rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) { SET_ERR(c, "weld scan failed"); return 20; }
-    hipLaunchKernelGGL(k_total_verts, dim3(1), dim3(1), 0, s,
-                       wscan, bits, nwords,
-                       (uint32_t *)c->lh_misc.ptr + 3);
-    uint32_t tv = 0;
-    HIP_TRY(c, hipMemcpyAsync(&tv, (uint32_t *)c->lh_misc.ptr + 3, 4,
-                              hipMemcpyDeviceToHost, s), 21);
-    HIP_TRY(c, hipStreamSynchronize(s), 21);
-    total_verts = tv;
-  }
-  c->stats.total_verts = total_verts;
-
-  if (ensure(c, c->verts, total_verts * 12)) return 22;
-  if (ensure(c, c->faces, NC * 4)) return 22;
-  if (ensure(c, c->vbase, ((uint64_t)nlabels + 1) * 4)) return 22;
-  {
-    int blk = 256;
-    uint64_t nbt = (T + blk - 1) / blk;
-    const float shift = voxel_centered ? 0.0f : 0.5f;
-    const uint64_t nwords = (NC + 63) / 64;
-    const unsigned long long *bits =
-        (const unsigned long long *)c->vtx_scan.ptr;
-    const uint32_t *wscan = (const uint32_t *)c->vtx_scan.ptr + 2 * nwords;
-    // vbase depends only on the scan, so it goes first
-    uint32_t nbl = (nlabels + 1 + 255) / 256;
-    hipLaunchKernelGGL(k_vbase, dim3(nbl), dim3(256), 0, s,
-                       (const uint32_t *)c->tri_off.ptr,
-                       wscan, bits,
-                       (uint32_t *)c->vbase.ptr, nlabels, total_verts);
-    hipLaunchKernelGGL(k_weld_verts_faces, dim3((uint32_t)nbt), dim3(blk), 0,
-                       s, corner_ent, lab_sorted, wscan, bits,
-                       (const uint32_t *)c->vbase.ptr,
-                       (float *)c->verts.ptr, (uint32_t *)c->faces.ptr,
-                       (uint32_t)g.sx, (uint32_t)(g.sx * g.sy),
-                       rx, ry, rz, shift, T);
-  }
-  HIP_TRY(c, hipGetLastError(), 22);
-  HIP_TRY(c, hipEventRecord(c->ev[6], s), 22);
-
-  // [6] per-label quadric simplification (mesh.py:376-381 semantics)
-  uint64_t Tcur = T, Vcur = total_verts;
-  if (reduction_factor > 1 && T > 0) {
-    int rc = run_simplify(c, nlabels, lab_sorted, reduction_factor,
-                          max_error, &Tcur, &Vcur);
-    if (rc) return rc;
-  }
-  HIP_TRY(c, hipEventRecord(c->ev[8], s), 22);
-  const uint64_t NCX = 3 * Tcur;
-
-  // [7] extract
-  mg_meshset *ms = nullptr;
-  if (flags_ & MG_FLAG_DEVICE_ONLY) {
-    HIP_TRY(c, hipStreamSynchronize(s), 23);
-    ms = (mg_meshset *)calloc(1, sizeof(mg_meshset) + 2 * sizeof(void *));
-    *out = ms;
-  } else {
-    if (ensure_host(c, c->h_verts, Vcur * 12 + 12)) return 24;
-    if (ensure_host(c, c->h_faces, NCX * 4 + 4)) return 24;
-    float *h_verts = (float *)c->h_verts.ptr;
-    uint32_t *h_faces = (uint32_t *)c->h_faces.ptr;
-    std::vector<uint32_t> h_tri_off(nlabels + 1), h_vbase(nlabels + 1);
-    std::vector<uint64_t> h_label_values(nlabels);
-    if (Vcur > 0)
-      HIP_TRY(c, hipMemcpyAsync(h_verts, c->verts.ptr, Vcur * 12,
-                                hipMemcpyDeviceToHost, s), 24);
-    if (NCX > 0)
-      HIP_TRY(c, hipMemcpyAsync(h_faces, c->faces.ptr, NCX * 4,
-                                hipMemcpyDeviceToHost, s), 24);
-    HIP_TRY(c, hipMemcpyAsync(h_tri_off.data(), c->tri_off.ptr,
-                              (nlabels + 1) * 4, hipMemcpyDeviceToHost, s), 24);
-    HIP_TRY(c, hipMemcpyAsync(h_vbase.data(), c->vbase.ptr, (nlabels + 1) * 4,
-                              hipMemcpyDeviceToHost, s), 24);
-    HIP_TRY(c, hipMemcpyAsync(h_label_values.data(), c->label_values.ptr,
-                              nlabels * 8, hipMemcpyDeviceToHost, s), 24);
-    HIP_TRY(c, hipStreamSynchronize(s), 24);
-
-    size_t meta_off = sizeof(mg_meshset) + sizeof(mg_mesh) * nlabels;
-    ms = (mg_meshset *)calloc(1, meta_off + (size_t)nlabels * 24);
-    ms->nmeshes = nlabels;
-    ms->meshes = (mg_mesh *)((char *)ms + sizeof(mg_meshset));
-    ms->verts_base = h_verts;
-    ms->faces_base = h_faces;
-    ms->total_verts = Vcur;
-    ms->total_tris = Tcur;
-    ms->labels_arr = (uint64_t *)((char *)ms + meta_off);
-    ms->voff_arr = (uint32_t *)(ms->labels_arr + nlabels);
-    ms->nv_arr = ms->voff_arr + nlabels;
-    ms->foff_arr = ms->nv_arr + nlabels;
-    ms->nf_arr = ms->foff_arr + nlabels;
-    // order meshes by ascending label value
-    std::vector<uint32_t> idx(nlabels);
-    for (uint32_t i = 0; i < nlabels; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
-      return h_label_values[a] < h_label_values[b];
-    });
-    for (uint32_t m = 0; m < nlabels; ++m) {
-      uint32_t l = idx[m];
-      mg_mesh &mm = ms->meshes[m];
-      mm.label = h_label_values[l];
-      mm.nverts = h_vbase[l + 1] - h_vbase[l];
-      mm.ntris = h_tri_off[l + 1] - h_tri_off[l];
-      mm.verts = h_verts + 3ull * h_vbase[l];
-      mm.faces = h_faces + 3ull * h_tri_off[l];
-      ms->labels_arr[m] = mm.label;
-      ms->voff_arr[m] = h_vbase[l];
-      ms->nv_arr[m] = mm.nverts;
-      ms->foff_arr[m] = h_tri_off[l];
-      ms->nf_arr[m] = mm.ntris;
-    }
-    *out = ms;
-  }
-  HIP_TRY(c, hipEventRecord(c->ev[7], s), 25);
-  HIP_TRY(c, hipStreamSynchronize(s), 25);
-
-  c->stats.ms_h2d = ev_ms(c, 0, 1);
-  c->stats.ms_count = ev_ms(c, 1, 2);
-  c->stats.ms_scan = ev_ms(c, 2, 3);
-  c->stats.ms_emit = ev_ms(c, 3, 4);
-  c->stats.ms_partition = ev_ms(c, 4, 5);
-  c->stats.ms_weld = ev_ms(c, 5, 6);
-  c->stats.ms_simplify = ev_ms(c, 6, 8);
-  c->stats.ms_d2h = ev_ms(c, 8, 7);
-  c->stats.ms_total = ev_ms(c, 0, 7);
-  if (fill_level) c->stats.ms_fill = ev_ms(c, 13, 14);
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
 // Standalone mesh simplification (multires LOD chain; see meshgine.h).
 // Reuses the per-label simplify machinery with ONE label spanning the
 // whole mesh.
-
-extern "C" int mg_simplify_mesh(mg_ctx *c,
-                                const float *verts, uint32_t nverts,
-                                const uint32_t *faces, uint32_t ntris,
-                                uint32_t reduction_factor, float max_error,
-                                const float **out_verts,
-                                uint32_t *out_nverts,
-                                const uint32_t **out_faces,
-                                uint32_t *out_ntris) {
+int mg_simplify_mesh(mg_ctx *c,
+                     const float *verts, uint32_t nverts,
+                     const uint32_t *faces, uint32_t ntris,
+                     uint32_t reduction_factor, float max_error,
+                     const float **out_verts, uint32_t *out_nverts,
+                     const uint32_t **out_faces, uint32_t *out_ntris) {
   if (!c) { SET_ERR(c, "null ctx"); return 1; }
   std::lock_guard<std::mutex> g(c->lock);
   c->err.clear();
@@ -2375,49 +2305,4 @@ extern "C" int mg_simplify_mesh(mg_ctx *c,
   return 0;
 }
 
-template <typename T>
-static int run_count_emit(mg_ctx *c, const T *d_labels, const GridDims &g,
-                          LabelHash lh, uint32_t *d_segcnt,
-                          uint32_t *d_segoff, uint64_t *p_total,
-                          uint32_t *p_nlabels) {
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipEventRecord(c->ev[1], s), 30);
-  int blk = 256;
-  int waves_per_blk = blk / WAVE;
-  int64_t nb = std::min<int64_t>(
-      (g.nseg + waves_per_blk - 1) / waves_per_blk, 8192);
-  nb = (nb + 7) & ~7ll;  // multiple of 8: XCD slab schedule coverage
-  hipLaunchKernelGGL(k_count<T>, dim3((uint32_t)nb), dim3(blk), 0, s,
-                     d_labels, g, d_segcnt, lh);
-  HIP_TRY(c, hipGetLastError(), 30);
-  HIP_TRY(c, hipEventRecord(c->ev[2], s), 30);
-
-  // check overflow + read label count
-  uint32_t misc[2] = {0, 0};
-  HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8, hipMemcpyDeviceToHost, s),
-          30);
-
-  // scan segcnt -> segoff
-  size_t tmp_bytes = 0;
-  hipError_t e = rocprim::exclusive_scan(
-      nullptr, tmp_bytes, d_segcnt, d_segoff, 0u, (size_t)g.nseg,
-      rocprim::plus<uint32_t>(), s);
-  if (e != hipSuccess) { SET_ERR(c, "seg scan size query failed"); return 30; }
-  if (ensure(c, c->scan_tmp, tmp_bytes)) return 30;
-  e = rocprim::exclusive_scan(
-      c->scan_tmp.ptr, tmp_bytes, d_segcnt, d_segoff, 0u, (size_t)g.nseg,
-      rocprim::plus<uint32_t>(), s);
-  if (e != hipSuccess) { SET_ERR(c, "seg scan failed"); return 30; }
-
-  uint32_t last_off = 0, last_cnt = 0;
-  HIP_TRY(c, hipMemcpyAsync(&last_off, d_segoff + (g.nseg - 1), 4,
-                            hipMemcpyDeviceToHost, s), 30);
-  HIP_TRY(c, hipMemcpyAsync(&last_cnt, d_segcnt + (g.nseg - 1), 4,
-                            hipMemcpyDeviceToHost, s), 30);
-  HIP_TRY(c, hipEventRecord(c->ev[3], s), 30);
-  HIP_TRY(c, hipStreamSynchronize(s), 30);
-  if (misc[1]) return -100;  // label hash overflow
-  *p_nlabels = misc[0];
-  *p_total = (uint64_t)last_off + last_cnt;
-  return 0;
-}
+}  // extern "C"

@@ -727,8 +727,8 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
   __shared__ uint32_t s_deg[WAVEMODE ? 1 : CAPV];
   __shared__ unsigned long long s_pick[CAPV];
   // optional LDS-resident CSR payload (face ids, u16) for rounds whose
-  // face count fits; costs 24 KB LDS -> fewer blocks/CU, so env-gated
-  // for A/B (MG_SIMP_CLLDS=0 disables; measured ~5% faster on, default on).
+  // face count fits; costs 24 KB LDS -> fewer blocks/CU. The host only
+  // launches CLLDS=false (measured-and-rejected).
   constexpr uint32_t CAPF = CLLDS ? 4096u : 1u;
   __shared__ uint16_t s_cl[3 * CAPF];
   // remap holds label-LOCAL canonical ids; LDS-resident when the label

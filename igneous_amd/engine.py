@@ -33,7 +33,7 @@ LABEL_MAP_LDS_MAX = 2048
 _EXPORTED_SYMBOLS = [
     "mg_init", "mg_destroy", "mg_mesh_chunk", "mg_mesh_chunk_mapped",
     "mg_mesh_chunk_filled", "mg_mesh_holes", "mg_fill_holes",
-    "mg_meshset_free",
+    "mg_simplify_mesh", "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
 ]
 
@@ -186,6 +186,28 @@ def load_library() -> ctypes.CDLL:
         return lib
 
 
+def _mg_dtype(arr: np.ndarray) -> int:
+    """MG_U32 / MG_U64 for a label array."""
+    if arr.dtype == np.uint32:
+        return MG_U32
+    if arr.dtype == np.uint64:
+        return MG_U64
+    raise ValueError(f"unsupported label dtype {arr.dtype}")
+
+
+def _default_device() -> int:
+    """Device of the module-level calls: MESHGINE_DEVICE, else LOCAL_RANK."""
+    return int(os.environ.get("MESHGINE_DEVICE",
+                              os.environ.get("LOCAL_RANK", "0")))
+
+
+def _fill_level_unsupported(what: str) -> NotImplementedError:
+    return NotImplementedError(
+        f"{what}: the engine implements levels "
+        f"1-2; level 3 needs a multilabel dilation and levels >= 4 "
+        f"a merge threshold")
+
+
 # When True, Engine.get() returns one context (and HIP stream) per
 # (device, thread): concurrent MeshTasks on one GPU overlap their
 # H2D / kernels / D2H — the reference's "one HIP stream per in-flight
@@ -224,6 +246,14 @@ class Engine:
                 cls._per_device[key] = eng
             return eng
 
+    def _check(self, rc: int, fn: str) -> None:
+        """Raise the ctx's last error if the C call `fn` returned non-zero."""
+        if rc != 0:
+            err = self.lib.mg_last_error(self.ctx)
+            raise RuntimeError(
+                f"{fn} failed rc={rc}: "
+                f"{err.decode() if err else 'unknown'}")
+
     def mesh_chunk(self, labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                    reduction_factor: int = 0, max_error: float = 40.0,
                    voxel_centered: bool = True,
@@ -256,10 +286,7 @@ class Engine:
         reuses the first one's staging. Not combinable with skip_h2d."""
         fill_holes = int(fill_holes)
         if fill_holes < 0 or fill_holes > 2:
-            raise NotImplementedError(
-                f"fill_holes={fill_holes}: the engine implements levels "
-                f"1-2; level 3 needs a multilabel dilation and levels >= 4 "
-                f"a merge threshold")
+            raise _fill_level_unsupported(f"fill_holes={fill_holes}")
         if fill_holes and skip_h2d:
             raise ValueError(
                 "fill_holes cannot be combined with skip_h2d: the "
@@ -267,12 +294,7 @@ class Engine:
         if fill_holes:
             copy = True
         labels = np.asfortranarray(labels)
-        if labels.dtype == np.uint32:
-            dtype = MG_U32
-        elif labels.dtype == np.uint64:
-            dtype = MG_U64
-        else:
-            raise ValueError(f"unsupported label dtype {labels.dtype}")
+        dtype = _mg_dtype(labels)
         sx, sy, sz = labels.shape
         flags = (MG_FLAG_DEVICE_ONLY if device_only else 0) | \
                 (MG_FLAG_SKIP_H2D if skip_h2d else 0)
@@ -314,11 +336,7 @@ class Engine:
                 fn = "mg_mesh_chunk_mapped"
                 rc = self.lib.mg_mesh_chunk_mapped(
                     *args, ctypes.byref(cmap), ctypes.byref(out))
-            if rc != 0:
-                err = self.lib.mg_last_error(self.ctx)
-                raise RuntimeError(
-                    f"{fn} failed rc={rc}: "
-                    f"{err.decode() if err else 'unknown'}")
+            self._check(rc, fn)
             result = self._collect(out, copy)
             if not fill_holes:
                 return result
@@ -327,11 +345,7 @@ class Engine:
             rc = self.lib.mg_mesh_holes(
                 self.ctx, *args[6:12], flags & MG_FLAG_DEVICE_ONLY,
                 ctypes.byref(out))
-            if rc != 0:
-                err = self.lib.mg_last_error(self.ctx)
-                raise RuntimeError(
-                    f"mg_mesh_holes failed rc={rc}: "
-                    f"{err.decode() if err else 'unknown'}")
+            self._check(rc, "mg_mesh_holes")
             return result, self._collect(out, True)
 
     def _collect(self, out, copy: bool) -> dict:
@@ -387,17 +401,9 @@ class Engine:
         of productive 3-D rounds."""
         level = int(level)
         if level not in (1, 2):
-            raise NotImplementedError(
-                f"fill_holes level {level}: the engine implements levels "
-                f"1-2; level 3 needs a multilabel dilation and levels >= 4 "
-                f"a merge threshold")
+            raise _fill_level_unsupported(f"fill_holes level {level}")
         labels = np.asfortranarray(labels)
-        if labels.dtype == np.uint32:
-            dtype = MG_U32
-        elif labels.dtype == np.uint64:
-            dtype = MG_U64
-        else:
-            raise ValueError(f"unsupported label dtype {labels.dtype}")
+        dtype = _mg_dtype(labels)
         if labels.ndim != 3:
             raise ValueError("fill_holes expects a 3-D volume")
         sx, sy, sz = labels.shape
@@ -410,11 +416,7 @@ class Engine:
                 sx, sy, sz, dtype, level,
                 filled.ctypes.data_as(ctypes.c_void_p),
                 holes.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rounds))
-            if rc != 0:
-                err = self.lib.mg_last_error(self.ctx)
-                raise RuntimeError(
-                    f"mg_fill_holes failed rc={rc}: "
-                    f"{err.decode() if err else 'unknown'}")
+            self._check(rc, "mg_fill_holes")
         return filled, holes, int(rounds.value)
 
     def simplify_mesh(self, verts: np.ndarray, faces: np.ndarray,
@@ -429,19 +431,19 @@ class Engine:
         of = ctypes.POINTER(ctypes.c_uint32)()
         onv = ctypes.c_uint32()
         ont = ctypes.c_uint32()
-        rc = self.lib.mg_simplify_mesh(
-            self.ctx,
-            v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
-            f.ctypes.data_as(ctypes.c_void_p), f.shape[0],
-            int(reduction_factor), float(max_error),
-            ctypes.byref(ov), ctypes.byref(onv),
-            ctypes.byref(of), ctypes.byref(ont))
-        if rc != 0:
-            raise RuntimeError(
-                f"mg_simplify_mesh failed rc={rc}: "
-                f"{self.lib.mg_last_error(self.ctx).decode()}")
-        out_v = np.ctypeslib.as_array(ov, shape=(onv.value, 3)).copy()
-        out_f = np.ctypeslib.as_array(of, shape=(ont.value, 3)).copy()
+        # the results are views of the ctx's pinned staging: hold the lock
+        # until they are copied, or another thread's call overwrites them
+        with self._lock:
+            rc = self.lib.mg_simplify_mesh(
+                self.ctx,
+                v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
+                f.ctypes.data_as(ctypes.c_void_p), f.shape[0],
+                int(reduction_factor), float(max_error),
+                ctypes.byref(ov), ctypes.byref(onv),
+                ctypes.byref(of), ctypes.byref(ont))
+            self._check(rc, "mg_simplify_mesh")
+            out_v = np.ctypeslib.as_array(ov, shape=(onv.value, 3)).copy()
+            out_f = np.ctypeslib.as_array(of, shape=(ont.value, 3)).copy()
         return out_v, out_f
 
     def stats(self) -> dict:
@@ -460,8 +462,7 @@ def mesh_chunk(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
     """Module-level product mesher (the default MeshTask path). With
     fill_holes=1|2 returns the pair (filled_meshes, hole_meshes)."""
     if device_id is None:
-        device_id = int(os.environ.get("MESHGINE_DEVICE",
-                                       os.environ.get("LOCAL_RANK", "0")))
+        device_id = _default_device()
     return Engine.get(device_id).mesh_chunk(
         labels, resolution, reduction_factor, max_error, voxel_centered,
         dust_threshold=dust_threshold, copy=copy, label_map=label_map,
@@ -485,8 +486,7 @@ def fill_holes(labels: np.ndarray, level: int = 1,
     """Module-level hole filling -> (filled, holes, rounds); see
     Engine.fill_holes."""
     if device_id is None:
-        device_id = int(os.environ.get("MESHGINE_DEVICE",
-                                       os.environ.get("LOCAL_RANK", "0")))
+        device_id = _default_device()
     return Engine.get(device_id).fill_holes(labels, level)
 
 
@@ -501,8 +501,7 @@ def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,
         return Mesh(mesh.vertices.copy(), mesh.faces.copy(), id=mesh.id)
     rf = max(nt // target, 2)
     if device_id is None:
-        device_id = int(os.environ.get("MESHGINE_DEVICE",
-                                       os.environ.get("LOCAL_RANK", "0")))
+        device_id = _default_device()
     v, f = Engine.get(device_id).simplify_mesh(
         mesh.vertices, mesh.faces, rf, max_error)
     return Mesh(v, f, id=mesh.id)

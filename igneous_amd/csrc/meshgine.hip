@@ -417,11 +417,13 @@ __global__ void k_count(const T *__restrict__ labels, GridDims g,
   }
 }
 
-// Compact 8-B triangle record: {cell_lin, mask | (t<<8)}. The three weld
-// slots (edge axis, voxel, side) and the doubled vertex coordinates are
-// all recomputable from it via the case tables — consumers decode instead
-// of re-reading a fat 16-B record (the record stream dominated the MC
-// pipeline's HBM traffic at 16 B/tri).
+// Compact 8-B triangle record: {cell_lin, mask | (t<<8) | (zero<<11)},
+// t in bits 8-10, zero = {cx==0, cy==0, cz==0} in bits 11-13 (which lower
+// neighbour cells do not exist; the weld's first-occurrence test needs
+// it). The three weld slots (edge axis, voxel, side) and the doubled
+// vertex coordinates are all recomputable from it via the case tables —
+// consumers decode instead of re-reading a fat 16-B record (the record
+// stream dominated the MC pipeline's HBM traffic at 16 B/tri).
 //
 // slot = ((cell_lin*3 + comb[e]) << 1) | side, where comb[e] folds the
 // edge's voxel offset and axis; side = is the label the edge's UPPER
@@ -448,26 +450,6 @@ __device__ __forceinline__ void stage_decode_tables(
                         : ((MC_EDGE_DOFF[e][1] & 1) ? 1u : 2u);
     s_comb[e] = eoff * 3u + axis;
   }
-}
-
-// decode one corner's weld slot (v in 0..2)
-__device__ __forceinline__ uint32_t decode_rec_slot1(
-    uint2 rec, const uint16_t *s_pack, const uint32_t *s_comb, uint32_t v) {
-  const uint32_t pk =
-      s_pack[(rec.y & 255u) * MC_MAX_TRIS + (rec.y >> 8)];
-  const uint32_t nib = (pk >> (5u * v)) & 31u;
-  return ((rec.x * 3u + s_comb[nib & 15u]) << 1) | (nib >> 4);
-}
-
-__device__ __forceinline__ void decode_rec_slots(
-    uint2 rec, const uint16_t *s_pack, const uint32_t *s_comb,
-    uint32_t s[3]) {
-  const uint32_t cl3 = rec.x * 3u;
-  const uint32_t pk =
-      s_pack[(rec.y & 255u) * MC_MAX_TRIS + (rec.y >> 8)];
-  s[0] = ((cl3 + s_comb[pk & 15]) << 1) | ((pk >> 4) & 1);
-  s[1] = ((cl3 + s_comb[(pk >> 5) & 15]) << 1) | ((pk >> 9) & 1);
-  s[2] = ((cl3 + s_comb[(pk >> 10) & 15]) << 1) | ((pk >> 14) & 1);
 }
 
 // [3] emit: recompute counts, wave prefix, write one 8-B record + the
@@ -507,6 +489,8 @@ __global__ void k_emit(const T *__restrict__ labels, GridDims g,
     if (active) {
       uint32_t pos = base;
       const uint32_t cell_lin = (uint32_t)((cz * g.sy + cy) * g.sx + cx);
+      const uint32_t zero = (uint32_t)(cx == 0) | ((uint32_t)(cy == 0) << 1) |
+                            ((uint32_t)(cz == 0) << 2);
       #pragma unroll
       for (int i = 0; i < 8; ++i) {
         T L = c[i];
@@ -522,7 +506,7 @@ __global__ void k_emit(const T *__restrict__ labels, GridDims g,
         uint32_t lid = label_lookup(lh, (uint64_t)L);
         for (uint32_t t = 0; t < nt; ++t) {
           tri_label[pos] = lid;
-          tri_recs[pos] = make_uint2(cell_lin, mask | (t << 8));
+          tri_recs[pos] = make_uint2(cell_lin, mask | (t << 8) | (zero << 11));
           ++pos;
         }
       }
@@ -551,112 +535,85 @@ __global__ void k_label_ranges(const uint32_t *__restrict__ lab_sorted,
 // labels of the edge's two endpoint voxels, so (edge, side) is a
 // collision-free address — no hash, no probing, and label-partitioned
 // corner streams touch CONTIGUOUS table lines (the reference's spatial
-// locality survives). minp_enc stores ~(first position) via atomicMax so
-// the table zero-memsets (0 = "no position yet").
+// locality survives). wminp[slot] holds the slot's first stream position.
 //
 // slot = axis*nvox + linear_voxel(vx,vy,vz), doubled; axis = the key's
 // odd coordinate. Capacity bound: 6*nvox must fit in u32 (checked on the
 // host; matches the reference's own 32-bit mesher task bound,
 // igneous_cli/cli.py:1049-1052).
+//
+// Whether a corner is the first occurrence of its slot in its label's
+// stream is a function of its record alone. The partition is stable, so
+// a label's stream keeps emit order: cells in (z, y, x) order, then the
+// mask's triangles t ascending, then corners v = 0..2. An edge with the
+// label at exactly one endpoint crosses that label's mask in EVERY cell
+// holding the edge, and every crossing edge is used by the mask's
+// triangulation (pinned by tests/test_mc_table.py). So the first
+// occurrence sits in the lowest cell holding the edge — on each axis b
+// perpendicular to the edge, either the edge is on the cell's upper side
+// or c_b == 0 (MC_EDGE_NEED against the record's boundary bits) — at the
+// mask's first (t, v) using the edge (MC_TRI_FIRST).
 
-// [5a] record first (minimum) stream position per (edge, side).
-// One thread per TRIANGLE (reads its 16-B record once). A per-workgroup
-// LDS table pre-merges duplicate slots within the block's 768-corner
-// window (the label-partitioned stream is spatially coherent, so ~half
-// the corners repeat a slot seen moments earlier) — cutting the global
-// atomic count roughly in half.
-template <int BLK, int TPT>
-__global__ __launch_bounds__(BLK) void k_weld_insert(
-    const uint2 *__restrict__ tri_recs,   // emit order (8-B records)
-    const uint32_t *__restrict__ order,   // label partition permutation
-    uint32_t *__restrict__ slots_sorted,  // decoded 3 slots/tri (12 B) —
-                                          // downstream weld passes read
-                                          // plain slots, no case tables
+// [5a] one thread per TRIANGLE of the label-partitioned stream: decode
+// the three slots, write the slot triple, and for each first-occurrence
+// corner store its stream position into wminp with a plain store (one
+// writer per slot). The table is never cleared: every slot the fused
+// kernel reads was stored here, in this call, by its unique first corner.
+//
+// Flags leave as a bit array, one u64 word per 64 consecutive corners
+// (vertex ids come from a word-granular scan + popcount). A wave's 64
+// triangles are corners [192w, 192w+192) = words 3w..3w+2: three ballots,
+// one per v, re-interleaved into corner order by a second ballot per word.
+#define WELD_FIRST_BLK 256
+__global__ __launch_bounds__(WELD_FIRST_BLK) void k_weld_first(
+    const uint2 *__restrict__ tri_recs,   // 8-B records
+    const uint32_t *__restrict__ order,   // label partition permutation,
+                                          // or null: records already sorted
+    uint32_t *__restrict__ slots_sorted,  // decoded 3 slots/tri (12 B)
     uint32_t *__restrict__ wminp,
+    unsigned long long *__restrict__ bits,
     int64_t sx, int64_t sxy,
-    uint64_t ntris) {
-  // LDS table sized for ~BLK*TPT*3 corners at ~0.4 load; wider windows
-  // dedup more of a vertex's ~6 corner occurrences before the global
-  // atomics (the label-sorted stream is spatially coherent)
-  constexpr int WI_LDS_SLOTS = BLK * TPT * 4;
-  constexpr int LG = __builtin_ctz(WI_LDS_SLOTS);
-  __shared__ uint32_t lkey[WI_LDS_SLOTS];
-  __shared__ uint32_t lval[WI_LDS_SLOTS];
+    uint64_t ntris, uint64_t nwords) {
   __shared__ uint16_t s_pack[256 * MC_MAX_TRIS];
+  __shared__ uint8_t s_first[256 * MC_MAX_TRIS];
   __shared__ uint32_t s_comb[12];
+  __shared__ uint32_t s_need[12];
   stage_decode_tables(s_pack, s_comb, sx, sxy);
-  for (int k = threadIdx.x; k < WI_LDS_SLOTS; k += BLK) {
-    lkey[k] = 0;
-    lval[k] = 0;
-  }
+  for (int k = threadIdx.x; k < 256 * MC_MAX_TRIS; k += blockDim.x)
+    s_first[k] = MC_TRI_FIRST[k / MC_MAX_TRIS][k % MC_MAX_TRIS];
+  if (threadIdx.x < 12) s_need[threadIdx.x] = MC_EDGE_NEED[threadIdx.x];
   __syncthreads();
-  const uint64_t span0 = (uint64_t)blockIdx.x * BLK * TPT;
-  #pragma unroll
-  for (int rep = 0; rep < TPT; ++rep) {
-    uint64_t t = span0 + (uint64_t)rep * BLK + threadIdx.x;
-    if (t >= ntris) break;
-    uint2 rec = order ? tri_recs[order[t]] : tri_recs[t];
-    uint32_t s[3];
-    decode_rec_slots(rec, s_pack, s_comb, s);
-    slots_sorted[3 * t] = s[0];
-    slots_sorted[3 * t + 1] = s[1];
-    slots_sorted[3 * t + 2] = s[2];
+  const uint64_t t = (uint64_t)blockIdx.x * WELD_FIRST_BLK + threadIdx.x;
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  bool f[3] = {false, false, false};  // tail lanes contribute 0
+  if (t < ntris) {
+    const uint2 rec = order ? tri_recs[order[t]] : tri_recs[t];
+    const uint32_t ti = (rec.y & 255u) * MC_MAX_TRIS + ((rec.y >> 8) & 7u);
+    const uint32_t pk = s_pack[ti];
+    const uint32_t fb = s_first[ti];
+    const uint32_t interior = ~(rec.y >> 11) & 7u;  // axes with c_b > 0
+    const uint32_t cl3 = rec.x * 3u;
     #pragma unroll
     for (int v = 0; v < 3; ++v) {
-      uint32_t slot = s[v];
-      uint32_t enc = ~(uint32_t)(3 * t + v);
-      uint32_t key = slot + 1;
-      uint32_t h = (slot * 2654435761u) >> (32 - LG);
-      bool placed = false;
-      for (int probe = 0; probe < 32; ++probe) {
-        uint32_t cur = lkey[h];
-        if (cur == 0) cur = atomicCAS(&lkey[h], 0u, key);
-        if (cur == 0 || cur == key) {
-          atomicMax(&lval[h], enc);
-          placed = true;
-          break;
-        }
-        h = (h + 1) & (WI_LDS_SLOTS - 1);
-      }
-      if (!placed) atomicMax(&wminp[slot], enc);  // rare spill
+      const uint32_t nib = (pk >> (5 * v)) & 31u;
+      const uint32_t e = nib & 15u;
+      const uint32_t slot = ((cl3 + s_comb[e]) << 1) | (nib >> 4);
+      slots_sorted[3 * t + v] = slot;
+      f[v] = ((fb >> v) & 1u) && (s_need[e] & interior) == 0;
+      if (f[v]) wminp[slot] = (uint32_t)(3 * t + v);
     }
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < WI_LDS_SLOTS; k += BLK) {
-    uint32_t key = lkey[k];
-    if (key) atomicMax(&wminp[key - 1], lval[k]);
+  const unsigned long long bal[3] = {__ballot(f[0]), __ballot(f[1]),
+                                     __ballot(f[2])};
+  const uint64_t w0 = (t / WAVE) * 3;  // wave-uniform
+  #pragma unroll
+  for (uint32_t j = 0; j < 3; ++j) {
+    const uint32_t c = 64 * j + lane;  // corner within the wave's 192
+    const uint32_t q = c / 3, r = c - 3 * q;
+    const unsigned long long src = r == 0 ? bal[0] : (r == 1 ? bal[1] : bal[2]);
+    const unsigned long long word = __ballot((src >> q) & 1ull);
+    if (lane == j && w0 + j < nwords) bits[w0 + j] = word;
   }
-}
-
-// [5b] first-occurrence flags as a bit array: each wave handles 64
-// consecutive corners and ballots the flags into one u64 word. Vertex
-// ids then come from a word-granular scan + popcount instead of a full
-// per-element scan array.
-//
-// The pass keeps what it gathered: a corner that is NOT a first
-// occurrence has its entry of the slot-triple array overwritten in place
-// with its first stream position p = ~wminp[slot] (always < i), so
-// nothing after this pass reads wminp again. First occurrences keep the
-// slot (needed to decode the coordinates; their first position is i
-// itself). `bits` says which kind each entry is. Each thread writes only
-// the entry it read.
-__global__ void k_weld_flag_bits(uint32_t *__restrict__ corner_ent,
-                                 const uint32_t *__restrict__ wminp,
-                                 unsigned long long *__restrict__ bits,
-                                 uint64_t ncorners, uint64_t nwords) {
-  uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  uint64_t word = gid / 64;
-  if (word >= nwords) return;
-  uint32_t lane = (uint32_t)(gid & 63);
-  uint64_t i = word * 64 + lane;
-  bool flag = false;
-  if (i < ncorners) {
-    uint32_t p = ~wminp[corner_ent[i]];
-    flag = (p == (uint32_t)i);
-    if (!flag) corner_ent[i] = p;
-  }
-  unsigned long long m = __ballot(flag);
-  if (lane == 0) bits[word] = m;
 }
 
 struct PopcWord {
@@ -696,13 +653,14 @@ __global__ void k_vbase(const uint32_t *__restrict__ tri_off,
 // vertex id is a pure function of its first stream position p:
 // wscan[p>>6] + popc(bits[p>>6] below bit p&63). A flagged corner (first
 // occurrence, ~1/6 of corners) is its own first position: it takes the id
-// from its own word, decodes the coordinates from the slot its entry
-// still holds and writes the vertex. An unflagged corner's entry holds p
-// (stored by the flag pass); a label's corners are contiguous in the
-// stream, so that bits/wscan lookup (12 B per 64 corners) is cache-local.
+// from its own word, decodes the coordinates from its slot and writes the
+// vertex. An unflagged corner gathers p = wminp[slot]; a label's corners
+// are contiguous in the stream, so both that gather and the bits/wscan
+// lookup (12 B per 64 corners) are cache-local.
 // No vertex-id table: faces need nothing the vertex writes produce.
 // Label id from the sorted label array — the partition sort's key output.
-__global__ void k_weld_verts_faces(const uint32_t *__restrict__ corner_ent,
+__global__ void k_weld_verts_faces(const uint32_t *__restrict__ slots,
+                                   const uint32_t *__restrict__ wminp,
                                    const uint32_t *__restrict__ lab_sorted,
                                    const uint32_t *__restrict__ wscan,
                                    const unsigned long long *__restrict__ bits,
@@ -714,8 +672,7 @@ __global__ void k_weld_verts_faces(const uint32_t *__restrict__ corner_ent,
                                    uint64_t ntris) {
   uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntris) return;
-  const uint32_t e[3] = {corner_ent[3 * t], corner_ent[3 * t + 1],
-                         corner_ent[3 * t + 2]};
+  const uint32_t e[3] = {slots[3 * t], slots[3 * t + 1], slots[3 * t + 2]};
   const uint32_t base = vbase[lab_sorted[t]];
   // corners 3t..3t+2 straddle two words when they start at bit 62 or 63
   // (3 does not divide 64); the second word exists since 3t+2 < 3*ntris
@@ -752,7 +709,7 @@ __global__ void k_weld_verts_faces(const uint32_t *__restrict__ corner_ent,
       verts[3ull * vid + 1] = (0.5f * dy + shift) * ry;
       verts[3ull * vid + 2] = (0.5f * dz + shift) * rz;
     } else {
-      vid = vtx_id_of(wscan, bits, e[v]);
+      vid = vtx_id_of(wscan, bits, wminp[e[v]]);
     }
     faces[3 * t + v] = vid - base;
   }
@@ -1600,7 +1557,7 @@ struct ChunkCall {
   uint32_t *lab_sorted;
   const uint2 *rec_src;
   const uint32_t *order_sorted;
-  uint32_t *corner_ent;
+  uint32_t *slots;
 };
 
 static void set_hole_stash(mg_ctx *c, const ChunkCall &k) {
@@ -1806,7 +1763,7 @@ static int run_count_emit(mg_ctx *c, ChunkCall &k) {
 
 // [4] stable partition by label id. Default (MG_SORT_RECS=0 reverts):
 // the 8-B records ride the radix sort as its 64-bit VALUES, so the
-// weld insert reads them back SEQUENTIALLY instead of paying a
+// weld reads them back SEQUENTIALLY instead of paying a
 // random 8-B gather through the permutation.
 static int run_partition(mg_ctx *c, ChunkCall &k) {
   hipStream_t s = c->stream;
@@ -1815,7 +1772,7 @@ static int run_partition(mg_ctx *c, ChunkCall &k) {
   const bool sort_recs = !(sre && sre[0] == '0');
   if (ensure(c, c->keys_sorted, T * 20)) return 19;  // [sort-alt 8B] + [slot triples 12B]
   if (ensure(c, c->tri_label_alt, T * 4)) return 19;
-  k.corner_ent = (uint32_t *)c->keys_sorted.ptr + 2 * T;
+  k.slots = (uint32_t *)c->keys_sorted.ptr + 2 * T;
   const dim3 nb((uint32_t)((T + 255) / 256)), blk(256);
   unsigned end_bit = 1;
   while ((1u << end_bit) < k.nlabels) ++end_bit;
@@ -1866,23 +1823,18 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
   }
   if (ensure(c, c->wh_keys, wslots * 4)) return 20;   // wminp
   if (ensure(c, c->vtx_scan, NC * 4)) return 20;
-  HIP_TRY(c, hipMemsetAsync(c->wh_keys.ptr, 0, wslots * 4, s), 20);
+  // not cleared: k_weld_first stores every slot that is read afterwards
   uint32_t *wminp = (uint32_t *)c->wh_keys.ptr;
-  // slot triples; the flag pass turns non-first entries into first positions
-  uint32_t *corner_ent = k.corner_ent;
   const dim3 nbt((uint32_t)((T + 255) / 256)), blk(256);
-  hipLaunchKernelGGL((k_weld_insert<1024, 2>),
-                     dim3((uint32_t)((T + 2047) / 2048)), dim3(1024), 0, s,
-                     k.rec_src, k.order_sorted, corner_ent, wminp, k.g.sx,
-                     k.g.sx * k.g.sy, T);
-  // first-occurrence flags as a bit array + word-granular scan
-  // (the vtx_scan buffer is NC*4 bytes >= nwords*12)
+  // first positions + first-occurrence flags as a bit array, then a
+  // word-granular scan (the vtx_scan buffer is NC*4 bytes >= nwords*12)
   const uint64_t nwords = (NC + 63) / 64;
   unsigned long long *bits = (unsigned long long *)c->vtx_scan.ptr;
   uint32_t *wscan = (uint32_t *)c->vtx_scan.ptr + 2 * nwords;
-  hipLaunchKernelGGL(k_weld_flag_bits,
-                     dim3((uint32_t)((nwords * 64 + 255) / 256)), blk, 0, s,
-                     corner_ent, wminp, bits, NC, nwords);
+  hipLaunchKernelGGL(k_weld_first,
+                     dim3((uint32_t)((T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK)),
+                     dim3(WELD_FIRST_BLK), 0, s, k.rec_src, k.order_sorted,
+                     k.slots, wminp, bits, k.g.sx, k.g.sx * k.g.sy, T, nwords);
   if (int e = scan_u32(c, rocprim::make_transform_iterator(bits, PopcWord{}),
                        wscan, nwords, s, "weld scan size query failed",
                        "weld scan failed", 20))
@@ -1905,7 +1857,8 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
                      (const uint32_t *)wscan,
                      (const unsigned long long *)bits,
                      (uint32_t *)c->vbase.ptr, k.nlabels, k.V);
-  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s, corner_ent,
+  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s,
+                     (const uint32_t *)k.slots, (const uint32_t *)wminp,
                      k.lab_sorted, (const uint32_t *)wscan,
                      (const unsigned long long *)bits,
                      (const uint32_t *)c->vbase.ptr, (float *)c->verts.ptr,

@@ -125,6 +125,24 @@ def triangulate(loops):
     return tris
 
 
+def tri_first_bits(tris):
+    """Per triangle t of one mask: bit v set iff corner v's edge does not
+    appear in triangles 0..t-1 (its first use within the cell)."""
+    seen = set()
+    out = []
+    for t in tris:
+        out.append(sum(1 << v for v, e in enumerate(t) if e not in seen))
+        seen.update(t)
+    return out
+
+
+def edge_need(e):
+    """Bit b set iff axis b is perpendicular to edge e and the edge lies on
+    the cell's LOWER side in b: the cell at c_b - 1 holds the edge too and
+    comes first in emit order, unless c_b == 0."""
+    return sum(1 << b for b in range(3) if EDGE_DOFF[e][b] == 0)
+
+
 def check_orientation():
     """Every single-corner mask must produce one triangle whose normal
     points AWAY from the labeled corner (outward)."""
@@ -198,6 +216,20 @@ def main():
                 packs.append(p)
             packs += [0] * (maxt - len(packs))
             f.write("  {" + ", ".join(f"0x{v:04x}" for v in packs) + "},\n")
+        f.write("};\n\n")
+        f.write("// per-(mask,tri) first-use bits: bit v set iff corner v's edge\n")
+        f.write("// is not used by triangles 0..t-1 of the same mask\n")
+        f.write(f"MC_TABLE_QUAL unsigned char MC_TRI_FIRST[256][{maxt}] = {{\n")
+        for m in range(256):
+            bits = tri_first_bits(table[m])
+            bits += [0] * (maxt - len(bits))
+            f.write("  {" + ", ".join(str(v) for v in bits) + "},\n")
+        f.write("};\n\n")
+        f.write("// per edge: bit b set iff axis b is perpendicular to the edge\n")
+        f.write("// and the edge lies on the cell's lower side in b (the cell\n")
+        f.write("// below in b, if any, holds the edge too and is emitted first)\n")
+        f.write("MC_TABLE_QUAL unsigned char MC_EDGE_NEED[12] = {\n")
+        f.write("  " + ", ".join(str(edge_need(e)) for e in range(12)) + ",\n")
         f.write("};\n\n")
         f.write("// corner ids (a,b) of each edge, a < b (a = lower voxel)\n")
         f.write("MC_TABLE_QUAL unsigned char MC_EDGE_CORNERS[12][2] = {\n")

@@ -1,0 +1,883 @@
+// chunk_mesh.hip — grid-chunk and clip one mesh on the device (the
+// multires merge's zmesh.chunk_mesh call sites, reference multires.py:550
+// and :574). Included from meshgine.hip after the ctx helpers (mg_ctx,
+// ensure, scan_u32, sort_pairs, SET_ERR, HIP_TRY, empty_meshset).
+//
+// Contract: bit-equal to igneous_amd/meshops.py
+// chunk_mesh + consolidate — the same cells, the same dict order, the same
+// f32 vertex bits, the same u32 faces. Every f64 operation below is one
+// IEEE operation written the way the host function writes it
+// (-ffp-contract=off keeps a*b+c two roundings).
+//
+// Units of work:
+//   face      one input triangle
+//   pair      one (face, overlapped cell) combination, numbered face-major
+//             with the cell loop cx, cy, cz (cz innermost) inside a face —
+//             ascending pair number IS the host's emit order
+//   fragment  a pair's clipped polygon (k points, 0 when fewer than 3)
+//   corner    one polygon point; corner j >= 2 of a fragment also stands
+//             for the fan triangle (0, j-1, j)
+//
+// Schedule (kernel boundaries order the phases; no spin flags, no grid
+// sync, every loop bounded; atomics are min/max/or/count only):
+//   k_cm_face_count   per face: cell range, pair count, mesh cell bbox
+//   scan              pair offsets
+//   k_cm_pair         per pair: clip in registers/scratch -> point count,
+//                     sort key (dense cell id << 1 | is_boundary)
+//   sort_pairs        stable by key: per-cell stream order
+//   k_cm_frag_gather  point counts in stream order, cell-head flags
+//   scan x2           corner offsets, cell ordinals
+//   k_cm_emit         re-clip, f32 corners in stream order
+//   4 x (k_cm_weld_key + sort_pairs)   LSD sort of corners by
+//                     (cell, x, y, z), -0 canonicalised, stable from
+//                     stream order: a run's head is its first occurrence
+//   k_cm_heads, scan, k_cm_head_pos, k_cm_rep   corner -> first corner
+//   k_cm_faces        fan faces, degenerate drop, used-vertex flags
+//   scan x2           vertex ids, face slots
+//   k_cm_write        per-cell vertex and face slices
+//   k_cm_cell_meta    per-cell bases for the host descriptor
+
+#include <cmath>
+
+#define CM_BLK 256
+#define CM_MAXPTS 16               // per-thread polygon capacity (points)
+#define CM_CELL_LIM 1048576.0      // cell coordinates live in [-2^20, 2^20)
+#define CM_MAX_PAIRS (1ull << 31)
+#define CM_MAX_DENSE (1ull << 31)  // cells of the mesh's cell bounding box
+#define CM_MAX_CORNERS (1ull << 31)
+
+#define CM_ERR_CELL_RANGE 1u
+#define CM_ERR_FACE_CELLS 2u
+#define CM_ERR_POLY_OVERFLOW 4u
+
+struct CmGrid {
+  double scale[3];
+  double offset[3];
+};
+
+// dense numbering of the cells inside the mesh's cell bounding box,
+// lexicographic in (cx, cy, cz)
+struct CmDense {
+  int lo[3];
+  uint32_t ny, nz;
+};
+
+// scalars the host reads back; one 64-byte block at cm_misc
+struct CmMisc {
+  unsigned long long pairs;    // sum of per-face cell counts
+  unsigned long long corners;  // sum of fragment point counts
+  int bb_lo[3];
+  int bb_hi[3];
+  uint32_t err;
+  uint32_t pad[5];
+};
+
+static inline uint32_t cm_blocks(uint64_t n) {
+  return (uint32_t)((n + CM_BLK - 1) / CM_BLK);
+}
+
+// Cell range of face f (meshops.py:116-121). Returns false when a cell
+// coordinate leaves [-2^20, 2^20); lo/hi are then zeroed.
+__device__ __forceinline__ bool cm_face_range(
+    const float *__restrict__ verts, const uint32_t *__restrict__ faces,
+    uint64_t f, const CmGrid &g, double tri[3][3], int lo[3], int hi[3]) {
+  for (int v = 0; v < 3; ++v) {
+    uint64_t vi = faces[3 * f + v];
+    for (int a = 0; a < 3; ++a) tri[v][a] = (double)verts[3 * vi + a];
+  }
+  bool ok = true;
+  for (int a = 0; a < 3; ++a) {
+    double mn = fmin(fmin(tri[0][a], tri[1][a]), tri[2][a]);
+    double mx = fmax(fmax(tri[0][a], tri[1][a]), tri[2][a]);
+    double l = floor((mn - g.offset[a]) / g.scale[a]);
+    double h = floor((mx - g.offset[a]) / g.scale[a] - 1e-12);
+    h = fmax(h, l);
+    if (!(l >= -CM_CELL_LIM && h < CM_CELL_LIM)) ok = false;
+    lo[a] = ok ? (int)l : 0;
+    hi[a] = ok ? (int)h : 0;
+  }
+  if (!ok)
+    for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
+  return ok;
+}
+
+// One Sutherland-Hodgman pass against an axis plane (meshops.py:82-98).
+// Never writes past CM_MAXPTS points; *ovf reports a dropped point.
+__device__ __forceinline__ int cm_clip_axis(const double (*in)[3], int n,
+                                            double (*out)[3], int a,
+                                            double bound, bool keep_below,
+                                            bool *ovf) {
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    const double *cur = in[i];
+    const double *nxt = in[i + 1 == n ? 0 : i + 1];
+    bool cin = keep_below ? (cur[a] <= bound) : (cur[a] >= bound);
+    bool nin = keep_below ? (nxt[a] <= bound) : (nxt[a] >= bound);
+    if (cin) {
+      if (m < CM_MAXPTS) {
+        out[m][0] = cur[0];
+        out[m][1] = cur[1];
+        out[m][2] = cur[2];
+        ++m;
+      } else {
+        *ovf = true;
+      }
+    }
+    if (cin != nin) {
+      double t = (bound - cur[a]) / (nxt[a] - cur[a]);
+      if (m < CM_MAXPTS) {
+        for (int k = 0; k < 3; ++k) {
+          double d = nxt[k] - cur[k];
+          double td = t * d;
+          out[m][k] = cur[k] + td;
+        }
+        ++m;
+      } else {
+        *ovf = true;
+      }
+    }
+  }
+  return m;
+}
+
+// Clip the triangle in A against cell (cx,cy,cz) (meshops.py:164-172).
+// The result is left in A; returns its point count, 0 if fewer than 3.
+__device__ __forceinline__ int cm_clip_cell(double (*A)[3], double (*B)[3],
+                                            const CmGrid &g, const int cell[3],
+                                            bool *ovf) {
+  int n = 3;
+  for (int a = 0; a < 3; ++a) {
+    double cs = (double)cell[a] * g.scale[a];
+    double bmin = g.offset[a] + cs;
+    double bmax = bmin + g.scale[a];
+    int m = cm_clip_axis(A, n, B, a, bmin, false, ovf);
+    n = cm_clip_axis(B, m, A, a, bmax, true, ovf);
+    if (n < 3) break;
+  }
+  return n >= 3 ? n : 0;
+}
+
+// the face owning pair p: largest f with pair_off[f] <= p (pair_off is
+// strictly increasing, pair_off[ntris] = number of pairs)
+__device__ __forceinline__ uint32_t cm_face_of_pair(
+    const uint32_t *__restrict__ pair_off, uint32_t ntris, uint32_t p) {
+  uint32_t lo = 0, hi = ntris;  // answer in [lo, hi)
+  for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+    uint32_t mid = lo + (hi - lo) / 2;
+    if (pair_off[mid] <= p) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// cell q of a face's range, in the host's loop order (cx outer, cz inner)
+__device__ __forceinline__ void cm_cell_of(const int lo[3], const int hi[3],
+                                           uint32_t q, int cell[3]) {
+  uint32_t dy = (uint32_t)(hi[1] - lo[1]) + 1u;
+  uint32_t dz = (uint32_t)(hi[2] - lo[2]) + 1u;
+  cell[2] = lo[2] + (int)(q % dz);
+  uint32_t r = q / dz;
+  cell[1] = lo[1] + (int)(r % dy);
+  cell[0] = lo[0] + (int)(r / dy);
+}
+
+__global__ __launch_bounds__(CM_BLK) void k_cm_face_count(
+    const float *__restrict__ verts, const uint32_t *__restrict__ faces,
+    uint32_t ntris, CmGrid g, uint32_t *__restrict__ ncells, CmMisc *misc) {
+  __shared__ int s_lo[3], s_hi[3];
+  if (threadIdx.x < 3) {
+    s_lo[threadIdx.x] = INT32_MAX;
+    s_hi[threadIdx.x] = INT32_MIN;
+  }
+  __syncthreads();
+  uint64_t f = (uint64_t)blockIdx.x * CM_BLK + threadIdx.x;
+  if (f < ntris) {
+    double tri[3][3];
+    int lo[3], hi[3];
+    uint32_t nc = 1;
+    if (!cm_face_range(verts, faces, f, g, tri, lo, hi)) {
+      atomicOr(&misc->err, CM_ERR_CELL_RANGE);
+    } else {
+      uint64_t n64 = (uint64_t)(hi[0] - lo[0] + 1) *
+                     (uint64_t)(hi[1] - lo[1] + 1) *
+                     (uint64_t)(hi[2] - lo[2] + 1);
+      if (n64 > CM_MAX_PAIRS) {
+        atomicOr(&misc->err, CM_ERR_FACE_CELLS);
+      } else {
+        nc = (uint32_t)n64;
+        for (int a = 0; a < 3; ++a) {
+          atomicMin(&s_lo[a], lo[a]);
+          atomicMax(&s_hi[a], hi[a]);
+        }
+      }
+    }
+    ncells[f] = nc;
+    atomicAdd(&misc->pairs, (unsigned long long)nc);
+  } else if (f == ntris) {
+    ncells[f] = 0;  // scan terminator: pair_off[ntris] = total
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && s_lo[threadIdx.x] <= s_hi[threadIdx.x]) {
+    atomicMin(&misc->bb_lo[threadIdx.x], s_lo[threadIdx.x]);
+    atomicMax(&misc->bb_hi[threadIdx.x], s_hi[threadIdx.x]);
+  }
+}
+
+// decode pair p into its face's corners and its cell; returns whether the
+// face is interior (one cell on every axis)
+__device__ __forceinline__ bool cm_pair_setup(
+    const float *__restrict__ verts, const uint32_t *__restrict__ faces,
+    const uint32_t *__restrict__ pair_off, uint32_t ntris, const CmGrid &g,
+    uint32_t p, double tri[3][3], int cell[3], uint32_t *p_face) {
+  uint32_t f = cm_face_of_pair(pair_off, ntris, p);
+  int lo[3], hi[3];
+  (void)cm_face_range(verts, faces, f, g, tri, lo, hi);
+  cm_cell_of(lo, hi, p - pair_off[f], cell);
+  *p_face = f;
+  return lo[0] == hi[0] && lo[1] == hi[1] && lo[2] == hi[2];
+}
+
+__global__ __launch_bounds__(CM_BLK) void k_cm_pair(
+    const float *__restrict__ verts, const uint32_t *__restrict__ faces,
+    const uint32_t *__restrict__ pair_off, uint32_t ntris, uint32_t npairs,
+    CmGrid g, CmDense dn, uint32_t *__restrict__ keys,
+    uint32_t *__restrict__ vals, uint32_t *__restrict__ npts, CmMisc *misc) {
+  uint64_t p = (uint64_t)blockIdx.x * CM_BLK + threadIdx.x;
+  if (p >= npairs) return;
+  double A[CM_MAXPTS][3], B[CM_MAXPTS][3];
+  int cell[3];
+  uint32_t f;
+  bool interior = cm_pair_setup(verts, faces, pair_off, ntris, g,
+                                (uint32_t)p, A, cell, &f);
+  int k = 3;
+  if (!interior) {
+    bool ovf = false;
+    k = cm_clip_cell(A, B, g, cell, &ovf);
+    if (ovf) {
+      atomicOr(&misc->err, CM_ERR_POLY_OVERFLOW);
+      k = 0;
+    }
+  }
+  uint32_t dense = ((uint32_t)(cell[0] - dn.lo[0]) * dn.ny +
+                    (uint32_t)(cell[1] - dn.lo[1])) * dn.nz +
+                   (uint32_t)(cell[2] - dn.lo[2]);
+  keys[p] = (dense << 1) | (interior ? 0u : 1u);
+  vals[p] = (uint32_t)p;
+  npts[p] = (uint32_t)k;
+  atomicAdd(&misc->corners, (unsigned long long)k);
+}
+
+// point counts in stream order + cell-head flags (index npairs: scan
+// terminators)
+__global__ void k_cm_frag_gather(const uint32_t *__restrict__ keys_s,
+                                 const uint32_t *__restrict__ order,
+                                 const uint32_t *__restrict__ npts,
+                                 uint32_t npairs,
+                                 uint32_t *__restrict__ npts_s,
+                                 uint32_t *__restrict__ head) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < npairs) {
+    npts_s[i] = npts[order[i]];
+    head[i] = (i == 0 || (keys_s[i] >> 1) != (keys_s[i - 1] >> 1)) ? 1u : 0u;
+  } else if (i == npairs) {
+    npts_s[i] = 0;
+    head[i] = 0;
+  }
+}
+
+// per-cell table, five sub-arrays of stride (ncellp + 1)
+enum { CM_CELL_C0 = 0, CM_CELL_DENSE, CM_CELL_FIRSTP, CM_CELL_VB, CM_CELL_FB,
+       CM_CELL_FIELDS };
+
+__global__ __launch_bounds__(CM_BLK) void k_cm_emit(
+    const float *__restrict__ verts, const uint32_t *__restrict__ faces,
+    const uint32_t *__restrict__ pair_off, uint32_t ntris, uint32_t npairs,
+    CmGrid g, const uint32_t *__restrict__ keys_s,
+    const uint32_t *__restrict__ order, const uint32_t *__restrict__ coff,
+    const uint32_t *__restrict__ head, const uint32_t *__restrict__ cord_x,
+    uint32_t ncorners, uint32_t cstride, float *__restrict__ pos,
+    uint32_t *__restrict__ cfrag, uint32_t *__restrict__ ccell,
+    uint32_t *__restrict__ cells) {
+  uint64_t i = (uint64_t)blockIdx.x * CM_BLK + threadIdx.x;
+  if (i >= npairs) return;
+  uint32_t ord = cord_x[i] + head[i] - 1u;  // cell ordinal of fragment i
+  uint32_t c0 = coff[i];
+  uint32_t k = coff[i + 1] - c0;
+  if (head[i]) {
+    cells[(uint64_t)CM_CELL_C0 * cstride + ord] = c0;
+    cells[(uint64_t)CM_CELL_DENSE * cstride + ord] = keys_s[i];
+  }
+  if (k == 0) return;
+  double A[CM_MAXPTS][3], B[CM_MAXPTS][3];
+  int cell[3];
+  uint32_t f;
+  bool interior = cm_pair_setup(verts, faces, pair_off, ntris, g, order[i],
+                                A, cell, &f);
+  int n = 3;
+  if (!interior) {
+    bool ovf = false;
+    n = cm_clip_cell(A, B, g, cell, &ovf);
+  }
+  // same inputs, same arithmetic as k_cm_pair: n == k. The bound keeps the
+  // writes inside the fragment's slice whatever happens.
+  for (uint32_t j = 0; j < k && j < (uint32_t)n && j < CM_MAXPTS; ++j) {
+    uint64_t c = (uint64_t)c0 + j;
+    if (c >= ncorners) break;
+    pos[3 * c + 0] = (float)A[j][0];
+    pos[3 * c + 1] = (float)A[j][1];
+    pos[3 * c + 2] = (float)A[j][2];
+    cfrag[c] = (uint32_t)i;
+    ccell[c] = ord;
+  }
+}
+
+__device__ __forceinline__ uint32_t cm_canon(float v) {
+  uint32_t b = __float_as_uint(v);
+  return b == 0x80000000u ? 0u : b;  // -0.0 equals +0.0
+}
+
+// key of weld sort pass `which` (0: z, 1: y, 2: x, 3: cell ordinal) for
+// the corners in their current order
+__global__ void k_cm_weld_key(const uint32_t *__restrict__ cur,
+                              const float *__restrict__ pos,
+                              const uint32_t *__restrict__ ccell,
+                              uint32_t ncorners, int which,
+                              uint32_t *__restrict__ keys) {
+  uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ncorners) return;
+  uint32_t c = cur[j];
+  keys[j] = which == 3 ? ccell[c] : cm_canon(pos[3ull * c + (2 - which)]);
+}
+
+// run heads of the (cell, x, y, z)-sorted corners (index ncorners: scan
+// terminator)
+__global__ void k_cm_heads(const uint32_t *__restrict__ sorted,
+                           const float *__restrict__ pos,
+                           const uint32_t *__restrict__ ccell,
+                           uint32_t ncorners, uint32_t *__restrict__ head) {
+  uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > ncorners) return;
+  uint32_t h = 0;
+  if (j < ncorners) {
+    h = 1;
+    if (j > 0) {
+      uint32_t a = sorted[j], b = sorted[j - 1];
+      h = (ccell[a] != ccell[b] ||
+           cm_canon(pos[3ull * a + 0]) != cm_canon(pos[3ull * b + 0]) ||
+           cm_canon(pos[3ull * a + 1]) != cm_canon(pos[3ull * b + 1]) ||
+           cm_canon(pos[3ull * a + 2]) != cm_canon(pos[3ull * b + 2]))
+              ? 1u : 0u;
+    }
+  }
+  head[j] = h;
+}
+
+__global__ void k_cm_head_pos(const uint32_t *__restrict__ sorted,
+                              const uint32_t *__restrict__ head,
+                              const uint32_t *__restrict__ run_x,
+                              uint32_t ncorners,
+                              uint32_t *__restrict__ head_pos) {
+  uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < ncorners && head[j]) head_pos[run_x[j]] = sorted[j];
+}
+
+// rep[c] = the first corner (stream position) of c's cell with c's position
+__global__ void k_cm_rep(const uint32_t *__restrict__ sorted,
+                         const uint32_t *__restrict__ head,
+                         const uint32_t *__restrict__ run_x,
+                         const uint32_t *__restrict__ head_pos,
+                         uint32_t ncorners, uint32_t *__restrict__ rep) {
+  uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < ncorners) rep[sorted[j]] = head_pos[run_x[j] + head[j] - 1u];
+}
+
+// Fan triangle (0, j-1, j) at corner j >= 2 of each fragment: keep flag
+// after the weld, used flags on the welded vertices. Also records each
+// cell's first emitted pair (the host's dict order). `used` is zeroed by
+// the driver; index ncorners of keep is the scan terminator.
+__global__ void k_cm_faces(const uint32_t *__restrict__ cfrag,
+                           const uint32_t *__restrict__ ccell,
+                           const uint32_t *__restrict__ coff,
+                           const uint32_t *__restrict__ order,
+                           const uint32_t *__restrict__ rep,
+                           uint32_t ncorners, uint32_t cstride,
+                           uint32_t *__restrict__ keep,
+                           uint32_t *__restrict__ used,
+                           uint32_t *__restrict__ cells) {
+  uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > ncorners) return;
+  if (c == ncorners) {
+    keep[c] = 0;
+    return;
+  }
+  uint32_t i = cfrag[c];
+  uint32_t c0 = coff[i];
+  uint32_t ord = ccell[c];
+  if (c == cells[(uint64_t)CM_CELL_C0 * cstride + ord])
+    cells[(uint64_t)CM_CELL_FIRSTP * cstride + ord] = order[i];
+  uint32_t kp = 0;
+  if (c - c0 >= 2) {
+    uint32_t a = rep[c0], b = rep[c - 1], d = rep[c];
+    if (a != b && b != d && a != d) {
+      kp = 1;
+      used[a] = 1;
+      used[b] = 1;
+      used[d] = 1;
+    }
+  }
+  keep[c] = kp;
+}
+
+__global__ void k_cm_write(const uint32_t *__restrict__ cfrag,
+                           const uint32_t *__restrict__ ccell,
+                           const uint32_t *__restrict__ coff,
+                           const uint32_t *__restrict__ rep,
+                           const uint32_t *__restrict__ keep,
+                           const uint32_t *__restrict__ used,
+                           const uint32_t *__restrict__ vid_x,
+                           const uint32_t *__restrict__ fslot_x,
+                           const float *__restrict__ pos,
+                           const uint32_t *__restrict__ cells,
+                           uint32_t ncorners, float *__restrict__ out_v,
+                           uint32_t *__restrict__ out_f) {
+  uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncorners) return;
+  if (used[c]) {
+    uint64_t v = vid_x[c];
+    out_v[3 * v + 0] = pos[3 * c + 0];
+    out_v[3 * v + 1] = pos[3 * c + 1];
+    out_v[3 * v + 2] = pos[3 * c + 2];
+  }
+  if (keep[c]) {
+    uint32_t c0 = coff[cfrag[c]];
+    uint32_t vb = vid_x[cells[ccell[c]]];  // CM_CELL_C0 sub-array
+    uint64_t t = fslot_x[c];
+    out_f[3 * t + 0] = vid_x[rep[c0]] - vb;
+    out_f[3 * t + 1] = vid_x[rep[c - 1]] - vb;
+    out_f[3 * t + 2] = vid_x[rep[c]] - vb;
+  }
+}
+
+// vertex / face base of every cell; entry ncellp holds the totals
+__global__ void k_cm_cell_meta(const uint32_t *__restrict__ vid_x,
+                               const uint32_t *__restrict__ fslot_x,
+                               uint32_t ncellp, uint32_t ncorners,
+                               uint32_t cstride,
+                               uint32_t *__restrict__ cells) {
+  uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o > ncellp) return;
+  uint32_t c0 = o == ncellp ? ncorners
+                            : cells[(uint64_t)CM_CELL_C0 * cstride + o];
+  cells[(uint64_t)CM_CELL_VB * cstride + o] = vid_x[c0];
+  cells[(uint64_t)CM_CELL_FB * cstride + o] = fslot_x[c0];
+}
+
+// ---------------------------------------------------------------------------
+// host driver
+
+struct CmCall {
+  uint32_t nverts, ntris;
+  CmGrid g;
+  CmDense dn;
+  uint64_t ndense;   // cells in the mesh's cell bounding box
+  uint32_t P;        // pairs
+  uint32_t C;        // corners
+  uint32_t ncellp;   // cells that received a fragment
+};
+
+static inline unsigned cm_bits(uint64_t nvalues) {  // bits to hold 0..n-1
+  unsigned b = 1;
+  while (b < 32 && (1ull << b) < nvalues) ++b;
+  return b;
+}
+
+// Host-side validation: nothing out of contract reaches a kernel.
+static int cm_validate(mg_ctx *c, const float *verts, uint32_t nverts,
+                       const uint32_t *faces, uint32_t ntris,
+                       const double scale[3], const double offset[3]) {
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(scale[a]) || !std::isfinite(offset[a])) {
+      SET_ERR(c, "chunk_mesh: non-finite scale/offset on axis %d", a);
+      return 60;
+    }
+    if (!(scale[a] > 0.0)) {
+      SET_ERR(c, "chunk_mesh: scale[%d] = %g must be > 0", a, scale[a]);
+      return 60;
+    }
+  }
+  for (uint64_t i = 0; i < 3ull * ntris; ++i) {
+    if (faces[i] >= nverts) {
+      SET_ERR(c, "chunk_mesh: face %llu references vertex %u >= nverts %u",
+              (unsigned long long)(i / 3), faces[i], nverts);
+      return 60;
+    }
+  }
+  for (uint64_t i = 0; i < 3ull * nverts; ++i) {
+    if (!std::isfinite(verts[i])) {
+      SET_ERR(c, "chunk_mesh: vertex %llu is not finite",
+              (unsigned long long)(i / 3));
+      return 60;
+    }
+  }
+  return 0;
+}
+
+// [1] upload, per-face cell ranges, pair offsets, cell bounding box
+static int cm_count(mg_ctx *c, CmCall &k, const float *verts,
+                    const uint32_t *faces) {
+  hipStream_t s = c->stream;
+  const uint64_t T = k.ntris;
+  if (ensure(c, c->cm_verts, (uint64_t)k.nverts * 12 + 12)) return 61;
+  if (ensure(c, c->cm_faces, T * 12 + 12)) return 61;
+  if (ensure(c, c->cm_ncells, (T + 1) * 4)) return 61;
+  if (ensure(c, c->cm_pair_off, (T + 1) * 4)) return 61;
+  if (ensure(c, c->cm_misc, sizeof(CmMisc))) return 61;
+  CmMisc init = {};
+  for (int a = 0; a < 3; ++a) {
+    init.bb_lo[a] = INT32_MAX;
+    init.bb_hi[a] = INT32_MIN;
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->cm_misc.ptr, &init, sizeof(init),
+                            hipMemcpyHostToDevice, s), 61);
+  HIP_TRY(c, hipMemcpyAsync(c->cm_verts.ptr, verts, (uint64_t)k.nverts * 12,
+                            hipMemcpyHostToDevice, s), 61);
+  HIP_TRY(c, hipMemcpyAsync(c->cm_faces.ptr, faces, T * 12,
+                            hipMemcpyHostToDevice, s), 61);
+  hipLaunchKernelGGL(k_cm_face_count, dim3(cm_blocks(T + 1)), dim3(CM_BLK), 0,
+                     s, (const float *)c->cm_verts.ptr,
+                     (const uint32_t *)c->cm_faces.ptr, k.ntris, k.g,
+                     (uint32_t *)c->cm_ncells.ptr, (CmMisc *)c->cm_misc.ptr);
+  CmMisc m;
+  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.ptr, sizeof(m),
+                            hipMemcpyDeviceToHost, s), 61);
+  HIP_TRY(c, hipStreamSynchronize(s), 61);
+  if (m.err & CM_ERR_CELL_RANGE) {
+    SET_ERR(c, "chunk_mesh: a cell coordinate is outside [-2^20, 2^20)");
+    return 62;
+  }
+  if ((m.err & CM_ERR_FACE_CELLS) || m.pairs > CM_MAX_PAIRS) {
+    SET_ERR(c, "chunk_mesh: more than 2^31 (face, cell) pairs");
+    return 62;
+  }
+  k.P = (uint32_t)m.pairs;
+  uint64_t n[3];
+  for (int a = 0; a < 3; ++a) {
+    k.dn.lo[a] = m.bb_lo[a];
+    n[a] = (uint64_t)((int64_t)m.bb_hi[a] - m.bb_lo[a] + 1);
+  }
+  k.ndense = n[0] * n[1] * n[2];  // each factor <= 2^21: no overflow
+  if (k.ndense > CM_MAX_DENSE) {
+    SET_ERR(c, "chunk_mesh: the mesh's bounding box spans %llu cells "
+            "(limit 2^31)", (unsigned long long)k.ndense);
+    return 62;
+  }
+  k.dn.ny = (uint32_t)n[1];
+  k.dn.nz = (uint32_t)n[2];
+  return scan_u32(c, (uint32_t *)c->cm_ncells.ptr,
+                  (uint32_t *)c->cm_pair_off.ptr, T + 1, s,
+                  "chunk_mesh pair scan size query failed",
+                  "chunk_mesh pair scan failed", 63);
+}
+
+// [2] per-pair point counts and sort keys; [3] stable sort into the
+// per-cell stream order; corner offsets and cell ordinals
+static int cm_pairs(mg_ctx *c, CmCall &k,
+                    rocprim::double_buffer<uint32_t> &keys,
+                    rocprim::double_buffer<uint32_t> &vals) {
+  hipStream_t s = c->stream;
+  const uint64_t P = k.P;
+  if (ensure(c, c->cm_npts, P * 4 + 4)) return 64;
+  if (ensure(c, c->cm_npts_s, (P + 1) * 4)) return 64;
+  if (ensure(c, c->cm_fhead, (P + 1) * 4)) return 64;
+  if (ensure(c, c->cm_coff, (P + 1) * 4)) return 64;
+  if (ensure(c, c->cm_ford, (P + 1) * 4)) return 64;
+  hipLaunchKernelGGL(k_cm_pair, dim3(cm_blocks(P)), dim3(CM_BLK), 0, s,
+                     (const float *)c->cm_verts.ptr,
+                     (const uint32_t *)c->cm_faces.ptr,
+                     (const uint32_t *)c->cm_pair_off.ptr, k.ntris, k.P, k.g,
+                     k.dn, keys.current(), vals.current(),
+                     (uint32_t *)c->cm_npts.ptr, (CmMisc *)c->cm_misc.ptr);
+  if (int e = sort_pairs(c, keys, vals, P, 0, cm_bits(2 * k.ndense), s,
+                         "chunk_mesh fragment sort size query failed",
+                         "chunk_mesh fragment sort failed", 65))
+    return e;
+  hipLaunchKernelGGL(k_cm_frag_gather, dim3(cm_blocks(P + 1)), dim3(CM_BLK),
+                     0, s, keys.current(), vals.current(),
+                     (const uint32_t *)c->cm_npts.ptr, k.P,
+                     (uint32_t *)c->cm_npts_s.ptr,
+                     (uint32_t *)c->cm_fhead.ptr);
+  if (int e = scan_u32(c, (uint32_t *)c->cm_npts_s.ptr,
+                       (uint32_t *)c->cm_coff.ptr, P + 1, s,
+                       "chunk_mesh corner scan size query failed",
+                       "chunk_mesh corner scan failed", 65))
+    return e;
+  if (int e = scan_u32(c, (uint32_t *)c->cm_fhead.ptr,
+                       (uint32_t *)c->cm_ford.ptr, P + 1, s,
+                       "chunk_mesh cell scan size query failed",
+                       "chunk_mesh cell scan failed", 65))
+    return e;
+  CmMisc m;
+  uint32_t ncellp = 0;
+  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.ptr, sizeof(m),
+                            hipMemcpyDeviceToHost, s), 66);
+  HIP_TRY(c, hipMemcpyAsync(&ncellp, (uint32_t *)c->cm_ford.ptr + P, 4,
+                            hipMemcpyDeviceToHost, s), 66);
+  HIP_TRY(c, hipStreamSynchronize(s), 66);
+  if (m.err & CM_ERR_POLY_OVERFLOW) {
+    SET_ERR(c, "chunk_mesh: a clipped polygon exceeded %d points",
+            CM_MAXPTS);
+    return 67;
+  }
+  if (m.corners >= CM_MAX_CORNERS) {
+    SET_ERR(c, "chunk_mesh: %llu fragment corners (limit 2^31)",
+            (unsigned long long)m.corners);
+    return 67;
+  }
+  k.C = (uint32_t)m.corners;
+  k.ncellp = ncellp;
+  return 0;
+}
+
+// [4] corners in stream order
+static int cm_emit(mg_ctx *c, const CmCall &k, const uint32_t *keys_s,
+                   const uint32_t *order) {
+  hipStream_t s = c->stream;
+  const uint64_t C = k.C, stride = (uint64_t)k.ncellp + 1;
+  if (ensure(c, c->cm_pos, C * 12 + 12)) return 68;
+  if (ensure(c, c->cm_cfrag, C * 4 + 4)) return 68;
+  if (ensure(c, c->cm_ccell, C * 4 + 4)) return 68;
+  if (ensure(c, c->cm_cells, stride * CM_CELL_FIELDS * 4)) return 68;
+  // FIRSTP stays 0xFFFFFFFF for a cell whose fragments were all empty
+  HIP_TRY(c, hipMemsetAsync(c->cm_cells.ptr, 0xFF,
+                            stride * CM_CELL_FIELDS * 4, s), 68);
+  hipLaunchKernelGGL(k_cm_emit, dim3(cm_blocks(k.P)), dim3(CM_BLK), 0, s,
+                     (const float *)c->cm_verts.ptr,
+                     (const uint32_t *)c->cm_faces.ptr,
+                     (const uint32_t *)c->cm_pair_off.ptr, k.ntris, k.P, k.g,
+                     keys_s, order, (const uint32_t *)c->cm_coff.ptr,
+                     (const uint32_t *)c->cm_fhead.ptr,
+                     (const uint32_t *)c->cm_ford.ptr, k.C,
+                     (uint32_t)stride, (float *)c->cm_pos.ptr,
+                     (uint32_t *)c->cm_cfrag.ptr,
+                     (uint32_t *)c->cm_ccell.ptr,
+                     (uint32_t *)c->cm_cells.ptr);
+  return 0;
+}
+
+// [5] weld: rep[c] = first corner of c's cell at c's position
+static int cm_weld(mg_ctx *c, const CmCall &k) {
+  hipStream_t s = c->stream;
+  const uint64_t C = k.C;
+  if (ensure(c, c->cm_wkey, C * 4 + 4)) return 69;
+  if (ensure(c, c->cm_wkey_alt, C * 4 + 4)) return 69;
+  if (ensure(c, c->cm_wval, C * 4 + 4)) return 69;
+  if (ensure(c, c->cm_wval_alt, C * 4 + 4)) return 69;
+  if (ensure(c, c->cm_whead, (C + 1) * 4)) return 69;
+  if (ensure(c, c->cm_wrun, (C + 1) * 4)) return 69;
+  if (ensure(c, c->cm_head_pos, C * 4 + 4)) return 69;
+  if (ensure(c, c->cm_rep, C * 4 + 4)) return 69;
+  rocprim::double_buffer<uint32_t> keys((uint32_t *)c->cm_wkey.ptr,
+                                        (uint32_t *)c->cm_wkey_alt.ptr);
+  rocprim::double_buffer<uint32_t> vals((uint32_t *)c->cm_wval.ptr,
+                                        (uint32_t *)c->cm_wval_alt.ptr);
+  const float *pos = (const float *)c->cm_pos.ptr;
+  const uint32_t *ccell = (const uint32_t *)c->cm_ccell.ptr;
+  hipLaunchKernelGGL(k_iota, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
+                     vals.current(), C);
+  for (int which = 0; which < 4; ++which) {
+    hipLaunchKernelGGL(k_cm_weld_key, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
+                       (const uint32_t *)vals.current(), pos, ccell, k.C,
+                       which, keys.current());
+    unsigned bits = which == 3 ? cm_bits(k.ncellp) : 32u;
+    if (int e = sort_pairs(c, keys, vals, C, 0, bits, s,
+                           "chunk_mesh weld sort size query failed",
+                           "chunk_mesh weld sort failed", 70))
+      return e;
+  }
+  const uint32_t *sorted = vals.current();
+  uint32_t *whead = (uint32_t *)c->cm_whead.ptr;
+  uint32_t *wrun = (uint32_t *)c->cm_wrun.ptr;
+  hipLaunchKernelGGL(k_cm_heads, dim3(cm_blocks(C + 1)), dim3(CM_BLK), 0, s,
+                     sorted, pos, ccell, k.C, whead);
+  if (int e = scan_u32(c, whead, wrun, C + 1, s,
+                       "chunk_mesh run scan size query failed",
+                       "chunk_mesh run scan failed", 70))
+    return e;
+  hipLaunchKernelGGL(k_cm_head_pos, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
+                     sorted, (const uint32_t *)whead, (const uint32_t *)wrun,
+                     k.C, (uint32_t *)c->cm_head_pos.ptr);
+  hipLaunchKernelGGL(k_cm_rep, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
+                     sorted, (const uint32_t *)whead, (const uint32_t *)wrun,
+                     (const uint32_t *)c->cm_head_pos.ptr, k.C,
+                     (uint32_t *)c->cm_rep.ptr);
+  return 0;
+}
+
+// [6] faces, vertex ids, per-cell output slices
+static int cm_faces(mg_ctx *c, const CmCall &k, const uint32_t *order) {
+  hipStream_t s = c->stream;
+  const uint64_t C = k.C, stride = (uint64_t)k.ncellp + 1;
+  if (ensure(c, c->cm_keep, (C + 1) * 4)) return 71;
+  if (ensure(c, c->cm_used, (C + 1) * 4)) return 71;
+  if (ensure(c, c->cm_vid, (C + 1) * 4)) return 71;
+  if (ensure(c, c->cm_fslot, (C + 1) * 4)) return 71;
+  if (ensure(c, c->cm_out_v, C * 12 + 12)) return 71;
+  if (ensure(c, c->cm_out_f, C * 12 + 12)) return 71;
+  const uint32_t *cfrag = (const uint32_t *)c->cm_cfrag.ptr;
+  const uint32_t *ccell = (const uint32_t *)c->cm_ccell.ptr;
+  const uint32_t *coff = (const uint32_t *)c->cm_coff.ptr;
+  const uint32_t *rep = (const uint32_t *)c->cm_rep.ptr;
+  uint32_t *keep = (uint32_t *)c->cm_keep.ptr;
+  uint32_t *used = (uint32_t *)c->cm_used.ptr;
+  uint32_t *vid = (uint32_t *)c->cm_vid.ptr;
+  uint32_t *fslot = (uint32_t *)c->cm_fslot.ptr;
+  uint32_t *cells = (uint32_t *)c->cm_cells.ptr;
+  HIP_TRY(c, hipMemsetAsync(used, 0, (C + 1) * 4, s), 71);
+  hipLaunchKernelGGL(k_cm_faces, dim3(cm_blocks(C + 1)), dim3(CM_BLK), 0, s,
+                     cfrag, ccell, coff, order, rep, k.C, (uint32_t)stride,
+                     keep, used, cells);
+  if (int e = scan_u32(c, used, vid, C + 1, s,
+                       "chunk_mesh vertex scan size query failed",
+                       "chunk_mesh vertex scan failed", 72))
+    return e;
+  if (int e = scan_u32(c, keep, fslot, C + 1, s,
+                       "chunk_mesh face scan size query failed",
+                       "chunk_mesh face scan failed", 72))
+    return e;
+  if (C > 0)
+    hipLaunchKernelGGL(k_cm_write, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
+                     cfrag, ccell, coff, rep, (const uint32_t *)keep,
+                     (const uint32_t *)used, (const uint32_t *)vid,
+                     (const uint32_t *)fslot, (const float *)c->cm_pos.ptr,
+                     (const uint32_t *)cells, k.C, (float *)c->cm_out_v.ptr,
+                     (uint32_t *)c->cm_out_f.ptr);
+  hipLaunchKernelGGL(k_cm_cell_meta, dim3(cm_blocks(stride)), dim3(CM_BLK),
+                     0, s, (const uint32_t *)vid, (const uint32_t *)fslot,
+                     k.ncellp, k.C, (uint32_t)stride, cells);
+  return 0;
+}
+
+// the descriptor of a chunk_mesh result: the mg_meshset layout of
+// extract_meshset plus out_order[nmeshes] behind nf_arr
+static mg_meshset *cm_alloc_meshset(uint32_t n, uint32_t **p_order) {
+  size_t meta_off = sizeof(mg_meshset) + sizeof(mg_mesh) * n;
+  mg_meshset *ms =
+      (mg_meshset *)calloc(1, meta_off + (size_t)n * 28 + 2 * sizeof(void *));
+  if (!ms) return nullptr;
+  ms->nmeshes = n;
+  ms->meshes = (mg_mesh *)((char *)ms + sizeof(mg_meshset));
+  ms->labels_arr = (uint64_t *)((char *)ms + meta_off);
+  ms->voff_arr = (uint32_t *)(ms->labels_arr + n);
+  ms->nv_arr = ms->voff_arr + n;
+  ms->foff_arr = ms->nv_arr + n;
+  ms->nf_arr = ms->foff_arr + n;
+  *p_order = ms->nf_arr + n;
+  return ms;
+}
+
+// [7] D2H into the ctx's pinned staging + the descriptor: one mesh per
+// non-empty cell by ascending label (= lexicographic cell order), and the
+// host function's dict order in out_order.
+static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
+                      const uint32_t **out_order) {
+  hipStream_t s = c->stream;
+  const uint64_t stride = (uint64_t)k.ncellp + 1;
+  std::vector<uint32_t> cells(stride * CM_CELL_FIELDS);
+  HIP_TRY(c, hipMemcpyAsync(cells.data(), c->cm_cells.ptr,
+                            cells.size() * 4, hipMemcpyDeviceToHost, s), 73);
+  HIP_TRY(c, hipStreamSynchronize(s), 73);
+  const uint32_t *dense = &cells[CM_CELL_DENSE * stride];
+  const uint32_t *firstp = &cells[CM_CELL_FIRSTP * stride];
+  const uint32_t *vb = &cells[CM_CELL_VB * stride];
+  const uint32_t *fb = &cells[CM_CELL_FB * stride];
+  const uint64_t V = vb[k.ncellp], F = fb[k.ncellp];
+  if (ensure_host(c, c->h_verts, V * 12 + 12)) return 73;
+  if (ensure_host(c, c->h_faces, F * 12 + 12)) return 73;
+  float *h_verts = (float *)c->h_verts.ptr;
+  uint32_t *h_faces = (uint32_t *)c->h_faces.ptr;
+  if (V > 0)
+    HIP_TRY(c, hipMemcpyAsync(h_verts, c->cm_out_v.ptr, V * 12,
+                              hipMemcpyDeviceToHost, s), 73);
+  if (F > 0)
+    HIP_TRY(c, hipMemcpyAsync(h_faces, c->cm_out_f.ptr, F * 12,
+                              hipMemcpyDeviceToHost, s), 73);
+  HIP_TRY(c, hipStreamSynchronize(s), 73);
+
+  std::vector<uint32_t> live;  // cell ordinals with faces, ascending
+  for (uint32_t o = 0; o < k.ncellp; ++o)
+    if (fb[o + 1] > fb[o]) live.push_back(o);
+  const uint32_t n = (uint32_t)live.size();
+  uint32_t *order = nullptr;
+  mg_meshset *ms = cm_alloc_meshset(n, &order);
+  if (!ms) {
+    SET_ERR(c, "chunk_mesh: out of host memory");
+    return 73;
+  }
+  ms->verts_base = h_verts;
+  ms->faces_base = h_faces;
+  ms->total_verts = V;
+  ms->total_tris = F;
+  for (uint32_t m = 0; m < n; ++m) {
+    uint32_t o = live[m];
+    uint32_t d = dense[o] >> 1;
+    int64_t cz = (int64_t)(d % k.dn.nz) + k.dn.lo[2];
+    int64_t cy = (int64_t)((d / k.dn.nz) % k.dn.ny) + k.dn.lo[1];
+    int64_t cx = (int64_t)(d / k.dn.nz / k.dn.ny) + k.dn.lo[0];
+    mg_mesh &mm = ms->meshes[m];
+    mm.label = ((uint64_t)(cx + (1 << 20)) << 42) |
+               ((uint64_t)(cy + (1 << 20)) << 21) |
+               (uint64_t)(cz + (1 << 20));
+    mm.nverts = vb[o + 1] - vb[o];
+    mm.ntris = fb[o + 1] - fb[o];
+    mm.verts = h_verts + 3ull * vb[o];
+    mm.faces = h_faces + 3ull * fb[o];
+    ms->labels_arr[m] = mm.label;
+    ms->voff_arr[m] = vb[o];
+    ms->nv_arr[m] = mm.nverts;
+    ms->foff_arr[m] = fb[o];
+    ms->nf_arr[m] = mm.ntris;
+    order[m] = m;
+  }
+  // dict order: cells whose stream starts with an interior face (sort key
+  // bit 0 clear) in ascending cell order, then the rest by first emitted
+  // pair
+  std::stable_sort(order, order + n, [&](uint32_t a, uint32_t b) {
+    uint32_t oa = live[a], ob = live[b];
+    bool ia = !(dense[oa] & 1u), ib = !(dense[ob] & 1u);
+    if (ia != ib) return ia;
+    if (ia) return oa < ob;
+    return firstp[oa] < firstp[ob];
+  });
+  *out = ms;
+  *out_order = order;
+  return 0;
+}
+
+static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
+                          const uint32_t *faces, uint32_t ntris,
+                          const double scale[3], const double offset[3],
+                          mg_meshset **out, const uint32_t **out_order) {
+  if (int e = cm_validate(c, verts, nverts, faces, ntris, scale, offset))
+    return e;
+  CmCall k = {};
+  k.nverts = nverts;
+  k.ntris = ntris;
+  for (int a = 0; a < 3; ++a) {
+    k.g.scale[a] = scale[a];
+    k.g.offset[a] = offset[a];
+  }
+  if (int e = cm_count(c, k, verts, faces)) return e;
+  if (ensure(c, c->cm_fkey, (uint64_t)k.P * 4 + 4)) return 64;
+  if (ensure(c, c->cm_fkey_alt, (uint64_t)k.P * 4 + 4)) return 64;
+  if (ensure(c, c->cm_fval, (uint64_t)k.P * 4 + 4)) return 64;
+  if (ensure(c, c->cm_fval_alt, (uint64_t)k.P * 4 + 4)) return 64;
+  rocprim::double_buffer<uint32_t> keys((uint32_t *)c->cm_fkey.ptr,
+                                        (uint32_t *)c->cm_fkey_alt.ptr);
+  rocprim::double_buffer<uint32_t> vals((uint32_t *)c->cm_fval.ptr,
+                                        (uint32_t *)c->cm_fval_alt.ptr);
+  if (int e = cm_pairs(c, k, keys, vals)) return e;
+  if (int e = cm_emit(c, k, keys.current(), vals.current())) return e;
+  if (k.C > 0)
+    if (int e = cm_weld(c, k)) return e;
+  if (int e = cm_faces(c, k, vals.current())) return e;
+  return cm_extract(c, k, out, out_order);
+}

@@ -788,7 +788,16 @@ struct DeviceBuffers {
       map_tab, map_keys, map_vals,  // label map table + staged pairs
       // fill_holes: u32 working volume, union-find parents, per-root
       // neighbour min/max, rewrite counter, resident hole volume
-      fill_vol, fill_parent, fill_cmin, fill_cmax, fill_misc, holes;
+      fill_vol, fill_parent, fill_cmin, fill_cmax, fill_misc, holes,
+      // chunk_mesh (chunk_mesh.hip): inputs, per-face / per-pair /
+      // per-corner / per-cell arrays, the two sorts' double buffers, outputs
+      cm_verts, cm_faces, cm_ncells, cm_pair_off, cm_misc,
+      cm_fkey, cm_fkey_alt, cm_fval, cm_fval_alt,
+      cm_npts, cm_npts_s, cm_fhead, cm_coff, cm_ford,
+      cm_pos, cm_cfrag, cm_ccell, cm_cells,
+      cm_wkey, cm_wkey_alt, cm_wval, cm_wval_alt, cm_whead, cm_wrun,
+      cm_head_pos, cm_rep, cm_keep, cm_used, cm_vid, cm_fslot,
+      cm_out_v, cm_out_f;
 };
 
 // Timing / ordering events of one mesh_chunk_impl call. EV_H2D_END is
@@ -2077,6 +2086,8 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
   return 0;
 }
 
+#include "chunk_mesh.hip"
+
 extern "C" {
 
 int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
@@ -2256,6 +2267,40 @@ int mg_simplify_mesh(mg_ctx *c,
   *out_faces = (const uint32_t *)c->h_faces.ptr;
   *out_ntris = (uint32_t)T;
   return 0;
+}
+
+// Grid-chunk and clip one mesh (multires merge; see meshgine.h). The
+// pipeline is in chunk_mesh.hip.
+int mg_chunk_mesh(mg_ctx *c,
+                  const float *verts, uint32_t nverts,
+                  const uint32_t *faces, uint32_t ntris,
+                  const double scale[3], const double offset[3],
+                  mg_meshset **out, const uint32_t **out_order) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (!out || !out_order || !scale || !offset ||
+      (ntris > 0 && (!verts || !faces))) {
+    SET_ERR(c, "null argument");
+    return 1;
+  }
+  *out = nullptr;
+  *out_order = nullptr;
+  if (ntris > (1u << 31) / 3) {
+    SET_ERR(c, "mesh too large (%u tris)", ntris);
+    return 2;
+  }
+  if (ntris == 0) {
+    uint32_t *order = nullptr;
+    mg_meshset *ms = cm_alloc_meshset(0, &order);
+    if (!ms) { SET_ERR(c, "chunk_mesh: out of host memory"); return 73; }
+    *out = ms;
+    *out_order = order;
+    return 0;
+  }
+  HIP_TRY(c, hipSetDevice(c->device), 4);
+  return run_chunk_mesh(c, verts, nverts, faces, ntris, scale, offset, out,
+                        out_order);
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@ LABEL_MAP_LDS_MAX = 2048
 _EXPORTED_SYMBOLS = [
     "mg_init", "mg_destroy", "mg_mesh_chunk", "mg_mesh_chunk_mapped",
     "mg_mesh_chunk_filled", "mg_mesh_holes", "mg_fill_holes",
-    "mg_simplify_mesh", "mg_meshset_free",
+    "mg_simplify_mesh", "mg_chunk_mesh", "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
 ]
 
@@ -181,6 +181,15 @@ def load_library() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.c_uint32),
             ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
             ctypes.POINTER(ctypes.c_uint32),
+        ]
+        lib.mg_chunk_mesh.restype = ctypes.c_int
+        lib.mg_chunk_mesh.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(ctypes.POINTER(_MgMeshSet)),
+            ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
         ]
         _lib = lib
         return lib
@@ -446,6 +455,44 @@ class Engine:
             out_f = np.ctypeslib.as_array(of, shape=(ont.value, 3)).copy()
         return out_v, out_f
 
+    def chunk_mesh(self, verts: np.ndarray, faces: np.ndarray,
+                   scale, offset) -> dict:
+        """Grid-partition one mesh with clipping at the cell boundaries on
+        the GPU (mg_chunk_mesh; the zmesh.chunk_mesh replacement of
+        multires.py:550,574, bit-equal to meshops.chunk_mesh).
+        -> {(cx, cy, cz): (verts, faces)} with owned arrays, in the host
+        function's dict order."""
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+        sc = (ctypes.c_double * 3)(*[float(x) for x in scale])
+        off = (ctypes.c_double * 3)(*[float(x) for x in offset])
+        out = ctypes.POINTER(_MgMeshSet)()
+        order = ctypes.POINTER(ctypes.c_uint32)()
+        # the meshset aliases the ctx's pinned staging: hold the lock
+        # until it is copied out
+        with self._lock:
+            rc = self.lib.mg_chunk_mesh(
+                self.ctx,
+                v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
+                f.ctypes.data_as(ctypes.c_void_p), f.shape[0],
+                sc, off, ctypes.byref(out), ctypes.byref(order))
+            self._check(rc, "mg_chunk_mesh")
+            n = int(out.contents.nmeshes)
+            # read out_order before _collect frees the descriptor
+            idx = np.ctypeslib.as_array(order, shape=(n,)).tolist() \
+                if n else []
+            by_label = self._collect(out, True)
+        labels = list(by_label)  # ascending label = meshes[] order
+        mask = (1 << 21) - 1
+        bias = 1 << 20
+        result = {}
+        for i in idx:
+            lab = labels[i]
+            key = (((lab >> 42) & mask) - bias, ((lab >> 21) & mask) - bias,
+                   (lab & mask) - bias)
+            result[key] = by_label[lab]
+        return result
+
     def stats(self) -> dict:
         s = MgStatsFill()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
@@ -488,6 +535,17 @@ def fill_holes(labels: np.ndarray, level: int = 1,
     if device_id is None:
         device_id = _default_device()
     return Engine.get(device_id).fill_holes(labels, level)
+
+
+def chunk_mesh(mesh, scale, offset, device_id: Optional[int] = None):
+    """Module-level grid chunker (the default multires path): Mesh ->
+    {(cx, cy, cz): Mesh}, the shape and order of meshops.chunk_mesh."""
+    from .meshes import Mesh
+    if device_id is None:
+        device_id = _default_device()
+    cells = Engine.get(device_id).chunk_mesh(
+        mesh.vertices, mesh.faces, scale, offset)
+    return {key: Mesh(v, f, id=mesh.id) for key, (v, f) in cells.items()}
 
 
 def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,

@@ -13,7 +13,10 @@ task names and argument meanings:
 
 External-package replacements (all in-repo, from their published
 specs/algorithms — DESIGN.md §7):
-  zmesh.chunk_mesh / merge_close_vertices -> igneous_amd.meshops
+  zmesh.chunk_mesh                        -> the HIP engine's chunk_mesh
+        via the `set_chunker` seam (igneous_amd.meshops.chunk_mesh is the
+        bit-equal CPU checker)
+  merge_close_vertices                    -> igneous_amd.meshops
   zmesh.simplify_fqmr                     -> the HIP quadric simplifier
         via the `set_simplifier` seam (default: engine.simplify_mesh on
         the GPU; the pyfqmr aggressiveness/K error schedule is NOT
@@ -54,6 +57,7 @@ __all__ = [
     "process_mesh",
     "generate_lods",
     "set_simplifier",
+    "set_chunker",
 ]
 
 # ---------------------------------------------------------------------------
@@ -78,6 +82,31 @@ def _get_simplifier():
     def gpu_simplify(mesh: Mesh, target_count: int) -> Mesh:
         return engine.simplify_mesh(mesh, target_count)
     return gpu_simplify
+
+
+# Grid chunker seam, beside the simplifier's and with MeshTask's rule that
+# an injected mesher keeps the host sequence: an injected chunker wins;
+# with an injected simplifier (the CPU checker harness) chunking stays on
+# meshops.chunk_mesh; otherwise (the product path) it is the HIP engine's
+# chunk_mesh, which is bit-equal to the host function.
+# fn(mesh: Mesh, scale, offset) -> {(cx, cy, cz): Mesh}.
+
+_chunker_fn = None
+
+
+def set_chunker(fn) -> None:
+    """Test seam. Pass None to restore the default selection."""
+    global _chunker_fn
+    _chunker_fn = fn
+
+
+def _get_chunker():
+    if _chunker_fn is not None:
+        return _chunker_fn
+    if _simplifier_fn is not None:
+        return meshops.chunk_mesh
+    from .. import engine
+    return engine.chunk_mesh
 
 
 # ---------------------------------------------------------------------------
@@ -134,7 +163,7 @@ def determine_mesh_shape_from_lods(lods: List[Mesh]):
 def retriangulate_mesh(mesh: Mesh, offset, scale) -> Mesh:
     """Cut triangles at the UPPER octree level's cell boundaries so no
     triangle leaks across a coarser node (multires.py:546-553)."""
-    chunks = meshops.chunk_mesh(mesh, scale, offset)
+    chunks = _get_chunker()(mesh, scale, offset)
     if not chunks:
         return mesh
     new_mesh = Mesh.concatenate(*chunks.values(), id=mesh.id)
@@ -161,7 +190,7 @@ def create_octree_level_from_mesh(mesh: Mesh, chunk_shape, lod: int,
     if lod == num_lods - 1:
         return ([Mesh(mesh.vertices, mesh.faces, id=mesh.id)],
                 ((0, 0, 0),))
-    grid = meshops.chunk_mesh(mesh, scale, offset)
+    grid = _get_chunker()(mesh, scale, offset)
     if not grid:
         return ([], tuple())
     nodes, submeshes = zip(*sorted(

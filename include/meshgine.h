@@ -37,6 +37,9 @@
  *   mg_mesh_holes      — replaces the second Mesher.mesh(hole_labels) +
  *                        compute_meshes (mesh.py:234-235) on the hole
  *                        volume left resident by mg_mesh_chunk_filled.
+ *   mg_chunk_mesh      — replaces zmesh.chunk_mesh in the multires merge
+ *                        (multires.py:550,574): grid partition of one mesh
+ *                        with clipping at the cell boundaries.
  *   mg_meshset_free    — replaces Python GC of zmesh.Mesh objects.
  *   mg_last_error      — error text for the last failed call on this ctx.
  *
@@ -269,6 +272,40 @@ int mg_simplify_mesh(mg_ctx *ctx,
                      uint32_t reduction_factor, float max_error,
                      const float **out_verts, uint32_t *out_nverts,
                      const uint32_t **out_faces, uint32_t *out_ntris);
+
+/* Grid-partition ONE mesh with triangle clipping at the cell boundaries —
+ * replaces zmesh.chunk_mesh at the multires merge's two call sites
+ * (the reference's igneous/tasks/mesh/multires.py:550 retriangulate_mesh
+ * and :574 create_octree_level_from_mesh). Bit-equal to
+ * igneous_amd.meshops.chunk_mesh (the CPU checker; contract in DESIGN.md
+ * §7a): cell = floor((p - offset) / scale) in f64, Sutherland-Hodgman
+ * against each overlapped cell box, fan triangulation, then a per-cell
+ * exact-duplicate weld, degenerate-face drop and unused-vertex drop in
+ * first-seen order.
+ *   verts/faces   host arrays (float32 V*3 / uint32 T*3)
+ *   scale/offset  cell size and grid anchor in the verts' units (f64)
+ *   out           one mg_mesh per non-empty cell, label =
+ *                 ((cx+2^20)<<42) | ((cy+2^20)<<21) | (cz+2^20), so the
+ *                 ascending-label order of meshes[] is lexicographic cell
+ *                 order. Storage is ctx-owned pinned staging under the
+ *                 mg_simplify_mesh lifetime rule; free the descriptor with
+ *                 mg_meshset_free.
+ *   out_order     [nmeshes] indices into meshes[] in the checker's dict
+ *                 order (cells holding an interior face first, ascending;
+ *                 then the rest by first emitted fragment). Lives in the
+ *                 descriptor allocation: freed by mg_meshset_free.
+ * ntris == 0 returns an empty set. Errors (non-zero return +
+ * mg_last_error, never a fault, rejected before any kernel runs): a face
+ * index >= nverts, a non-finite vertex/scale/offset, a scale component
+ * <= 0. Rejected by the first device pass: a cell coordinate outside
+ * [-2^20, 2^20), more than 2^31 (face, cell) pairs, a cell bounding box
+ * of more than 2^31 cells, 2^31 or more fragment corners, a clipped
+ * polygon of more than 16 points. The ctx stays usable after any of them. */
+int mg_chunk_mesh(mg_ctx *ctx,
+                  const float *verts, uint32_t nverts,
+                  const uint32_t *faces, uint32_t ntris,
+                  const double scale[3], const double offset[3],
+                  mg_meshset **out, const uint32_t **out_order);
 
 /* Stats of the last mg_mesh_chunk on this ctx. Returns 0 on success. */
 int mg_get_stats(mg_ctx *ctx, mg_stats *out);

@@ -1092,10 +1092,6 @@ static double ev_ms(mg_ctx *c, int a, int b) {
 // oracle/simplify.c round for round.
 
 #define SIMP_BLK 256
-// labels up to SIMP_BIG_CAP faces simplify entirely inside one workgroup
-// each (cache-resident round loop, no global sorts); only bigger labels
-// go through the global-rounds machinery.
-#define SIMP_BIG_CAP 65536u
 
 static inline uint32_t simp_blocks(uint64_t n) {
   return (uint32_t)((n + SIMP_BLK - 1) / SIMP_BLK);
@@ -1223,8 +1219,8 @@ static int simp_launch_labels(mg_ctx *c, const SimpCall &k) {
   hipStream_t s = c->stream;
   auto launch_band = [&](auto fn, hipStream_t st, uint32_t nv_lo,
                          uint32_t nv_hi) {
-    hipLaunchKernelGGL(fn, dim3((uint32_t)k.L), dim3(256), 0, st,
-                       (uint32_t *)c->faces.ptr,
+    hipLaunchKernelGGL(fn, dim3((uint32_t)k.L), dim3(SIMP_LABEL_BS), 0,
+                       st, (uint32_t *)c->faces.ptr,
                        (uint32_t *)c->simp_faces_alt.ptr,
                        (const uint32_t *)c->tri_off.ptr,
                        (const uint32_t *)c->vbase.ptr,
@@ -1235,23 +1231,20 @@ static int simp_launch_labels(mg_ctx *c, const SimpCall &k) {
                        (uint32_t *)c->simp_adj.ptr,
                        (uint32_t *)c->simp_pk.ptr,
                        (SimpPlane *)c->simp_fq.ptr,
-                       (uint8_t *)c->simp_valid.ptr,
                        k.nt_cur, k.target, k.active,
                        (uint32_t *)c->simp_park.ptr, k.d_prof, k.d_rh,
                        k.max_cost, (uint32_t)k.L, SIMP_BIG_CAP, k.env.subs,
-                       nv_lo, nv_hi, 0u, 0xFFFFFFFFu,
-                       (uint32_t *)c->simp_accept.ptr, k.env.propose,
-                       (const uint32_t *)nullptr);
+                       nv_lo, nv_hi,
+                       (uint32_t *)c->simp_accept.ptr, k.env.propose);
   };
   // record BEFORE enqueuing the main band: stream2 must wait only for the
   // shared setup, so its bands run CONCURRENT with the main one
   // (recording after it serialized them — 51 ms vs 38 ms overlapped)
   HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_FORK], s), 40);
   HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SIMP_FORK], 0), 40);
-  launch_band(k_simplify_label<false, 256, 2048>, s, 0u, 2048u);
-  launch_band(k_simplify_label<false, 256, 4096>, c->stream2, 2048u, 4096u);
-  launch_band(k_simplify_label<false, 256, 2048>, c->stream2, 4096u,
-              0xFFFFFFFFu);
+  launch_band(k_simplify_label<2048>, s, 0u, 2048u);
+  launch_band(k_simplify_label<4096>, c->stream2, 2048u, 4096u);
+  launch_band(k_simplify_label<2048>, c->stream2, 4096u, 0xFFFFFFFFu);
   HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_JOIN], c->stream2), 40);
   HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_SIMP_JOIN], 0), 40);
   HIP_TRY(c, hipGetLastError(), 40);

@@ -72,8 +72,11 @@ __device__ __forceinline__ float sq_place(const float *S, float mx,
 }
 
 // cost-only form for the pick phase (identical arithmetic; the
-// placement registers don't outlive the call — keeps the per-label
-// kernel at <=128 VGPRs / 4 waves per SIMD)
+// placement registers don't outlive the call). Written out rather than
+// calling sq_place: the call form leaves the per-label kernel's
+// allocation as it is but takes k_edge_pick from 82 to 78 VGPRs, 5 to 6
+// waves per SIMD — an occupancy step that should move only in a change
+// that times the global-rounds path (simplifier cleanup).
 __device__ __forceinline__ float sq_place_cost(const float *S, float mx,
                                                float my, float mz) {
   float a00 = S[0], a01 = S[1], a02 = S[2], b0 = S[3];
@@ -99,6 +102,164 @@ __device__ __forceinline__ float sq_place_cost(const float *S, float mx,
   return cost;
 }
 
+// ---- collapse helpers shared by the global-rounds kernels and the
+// per-label kernel. Each is the one device copy of an oracle/simplify.c
+// expression; expression and operand order are the contract.
+
+// Unit plane of face (i0, i1, i2), global vertex ids. A degenerate face
+// gives the zero plane: accumulating it adds exact +0 products, bitwise
+// identical to the oracle's skip (quadric sums are never -0). A valid
+// plane has a unit normal, so it is never all zero.
+__device__ __forceinline__ SimpPlane
+sq_face_plane(const float *__restrict__ verts, uint32_t i0, uint32_t i1,
+              uint32_t i2) {
+  const float *p0 = verts + 3ull*i0, *p1 = verts + 3ull*i1,
+              *p2 = verts + 3ull*i2;
+  float ux = p1[0]-p0[0], uy = p1[1]-p0[1], uz = p1[2]-p0[2];
+  float vx = p2[0]-p0[0], vy = p2[1]-p0[1], vz = p2[2]-p0[2];
+  float nx = uy*vz - uz*vy, ny = uz*vx - ux*vz, nz = ux*vy - uy*vx;
+  float len = sqrtf(nx*nx + ny*ny + nz*nz);
+  if (len <= 0.0f) return SimpPlane{0.0f, 0.0f, 0.0f, 0.0f};
+  float inv = 1.0f / len;
+  nx *= inv; ny *= inv; nz *= inv;
+  float d = -(nx*p0[0] + ny*p0[1] + nz*p0[2]);
+  return SimpPlane{nx, ny, nz, d};
+}
+
+// Collapse the matched pair (u, w), global ids, u < w: u moves to the
+// placement of the summed quadric and absorbs w's quadric. The caller
+// owns the remap and pick stores.
+__device__ __forceinline__ void sq_collapse(float *__restrict__ verts,
+                                            float *__restrict__ Q,
+                                            uint64_t u, uint64_t w) {
+  float mx = 0.5f*(verts[3*u]+verts[3*w]);
+  float my = 0.5f*(verts[3*u+1]+verts[3*w+1]);
+  float mz = 0.5f*(verts[3*u+2]+verts[3*w+2]);
+  float S[10];
+  #pragma unroll
+  for (int k = 0; k < 10; ++k) S[k] = Q[12*u + k] + Q[12*w + k];
+  float px, py, pz;
+  (void)sq_place(S, mx, my, mz, &px, &py, &pz);
+  verts[3*u] = px; verts[3*u+1] = py; verts[3*u+2] = pz;
+  #pragma unroll
+  for (int k = 0; k < 10; ++k) Q[12*u + k] += Q[12*w + k];
+}
+
+// Edge picks of one face, in two steps around caller-owned staging arrays
+// (declared in the kernel and passed by reference: behind one helper that
+// owns them, the compiler allocates the per-label kernel's keep bitmask
+// differently and its scratch rises from 48 to 56 B/lane — DESIGN §4).
+//
+// Step 1: stage the 3 corner quadrics + positions in registers once per
+// face. Q rows are 12 floats (48 B, 16-B aligned), 3 dwordx4 loads each;
+// the a<b swap in step 2 defeats CSE of the Q loads otherwise, and
+// re-loading both quadrics per edge doubles the phase's traffic.
+__device__ __forceinline__ void
+sq_stage_corners(const uint32_t (&fc)[3], const float *__restrict__ verts,
+                 const float *__restrict__ Q, float (&cq)[3][10],
+                 float (&cp)[3][3]) {
+  #pragma unroll
+  for (int ci = 0; ci < 3; ++ci) {
+    const float4 *qp = (const float4 *)(Q + 12ull*fc[ci]);
+    float4 a = qp[0], b = qp[1], cc = qp[2];
+    cq[ci][0] = a.x; cq[ci][1] = a.y; cq[ci][2] = a.z; cq[ci][3] = a.w;
+    cq[ci][4] = b.x; cq[ci][5] = b.y; cq[ci][6] = b.z; cq[ci][7] = b.w;
+    cq[ci][8] = cc.x; cq[ci][9] = cc.y;
+    #pragma unroll
+    for (int k = 0; k < 3; ++k) cp[ci][k] = verts[3ull*fc[ci] + k];
+  }
+}
+
+// Step 2: every edge of the face (corners fc, global ids) whose collapse
+// cost is within max_cost bids (cost-bits<<32 | peer) for both ends'
+// cheapest-edge slots. pick is indexed by id - pick_base (0 for the global
+// table, the label's vertex base for a label-local one); vb is the label's
+// vertex base — the tie jitter works in label-LOCAL ids like
+// oracle/simplify.c.
+__device__ __forceinline__ void
+sq_edge_bids(const uint32_t (&fc)[3], const float (&cq)[3][10],
+             const float (&cp)[3][3], unsigned long long *pick,
+             uint32_t pick_base, uint32_t vb, float max_cost) {
+  #pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const int ea = e, eb = (e + 1) % 3;   // compile-time after unroll
+    uint32_t a = fc[ea], b = fc[eb];
+    if (a == b) continue;
+    // canonical u < w; addition is commutative-safe here only because
+    // both operand orders are evaluated identically (x+y) — keep the
+    // oracle's Q[u]+Q[w] order via selects on compile-time indices
+    bool fwd = a < b;
+    uint32_t u = fwd ? a : b, w = fwd ? b : a;
+    float mx = 0.5f*((fwd ? cp[ea][0] : cp[eb][0]) + (fwd ? cp[eb][0] : cp[ea][0]));
+    float my = 0.5f*((fwd ? cp[ea][1] : cp[eb][1]) + (fwd ? cp[eb][1] : cp[ea][1]));
+    float mz = 0.5f*((fwd ? cp[ea][2] : cp[eb][2]) + (fwd ? cp[eb][2] : cp[ea][2]));
+    float S[10];
+    #pragma unroll
+    for (int k = 0; k < 10; ++k)
+      S[k] = (fwd ? cq[ea][k] : cq[eb][k]) + (fwd ? cq[eb][k] : cq[ea][k]);
+    float cost = sq_place_cost(S, mx, my, mz);
+    if (cost > max_cost) continue;
+    uint32_t cb = __float_as_uint(cost);
+    // per-edge tie jitter — identical to oracle/simplify.c
+    uint32_t ul = u - vb, wl = w - vb;
+    uint32_t hsh = ul ^ (wl * 2654435761u);
+    hsh ^= hsh >> 16; hsh *= 2246822519u; hsh ^= hsh >> 13;
+    cb ^= (hsh & 7u);
+    atomicMin(&pick[u - pick_base], ((unsigned long long)cb << 32) | w);
+    atomicMin(&pick[w - pick_base], ((unsigned long long)cb << 32) | u);
+  }
+}
+
+// Quadric of one vertex of degree d <= W from its incident face ids
+// fl_in[0..d): sort them ascending in registers (bitonic network,
+// compile-time indices; the sorted order is unique because face ids are
+// distinct, so it matches the oracle's insertion sort exactly), then add
+// the planes in that order into q.
+template <int W>
+__device__ __forceinline__ void sq_sort_accum(float *q,
+                                              const uint32_t *fl_in,
+                                              uint32_t d,
+                                              const SimpPlane *pl) {
+  uint32_t fl[W];
+  #pragma unroll
+  for (int k = 0; k < W; ++k)
+    fl[k] = (k < (int)d) ? fl_in[k] : 0xFFFFFFFFu;
+  #pragma unroll
+  for (int ksz = 2; ksz <= W; ksz <<= 1) {
+    #pragma unroll
+    for (int j = ksz >> 1; j > 0; j >>= 1) {
+      #pragma unroll
+      for (int i = 0; i < W; ++i) {
+        int l = i ^ j;
+        if (l > i) {
+          bool up = ((i & ksz) == 0);
+          uint32_t a = fl[i], b2 = fl[l];
+          bool sw = up ? (a > b2) : (a < b2);
+          fl[i] = sw ? b2 : a;
+          fl[l] = sw ? a : b2;
+        }
+      }
+    }
+  }
+  // gather planes in 8-batches (8 independent loads in flight each) —
+  // staging all 16 at once cost 64 VGPRs and pushed the per-label kernel
+  // past the 128-VGPR / 4-waves-per-SIMD occupancy step. Accumulation
+  // order (ascending fl) is unchanged.
+  #pragma unroll
+  for (int h = 0; h < W / 8; ++h) {
+    SimpPlane ps[8];
+    #pragma unroll
+    for (int k = 0; k < 8; ++k)
+      // pad with face 0 (the label has >= 1 face); fl[k] is the
+      // 0xFFFFFFFF sort sentinel beyond d, must not be indexed
+      ps[k] = pl[8*h + k < (int)d ? fl[8*h + k] : 0u];
+    #pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (8*h + k < (int)d)
+        sq_add_plane(q, ps[k].nx, ps[k].ny, ps[k].nz, ps[k].d, 1.0f);
+  }
+}
+
 // [S1] per-face plane (recomputed each round; verts move)
 __global__ void k_face_planes(const uint32_t *__restrict__ faces_g,
                               const float *__restrict__ verts,
@@ -110,24 +271,10 @@ __global__ void k_face_planes(const uint32_t *__restrict__ faces_g,
   uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntris) return;
   if (!active_lab[flab[t]]) { fvalid[t] = 0; return; }
-  uint32_t i0 = faces_g[3*t], i1 = faces_g[3*t+1], i2 = faces_g[3*t+2];
-  const float *p0 = verts + 3*i0, *p1 = verts + 3*i1, *p2 = verts + 3*i2;
-  float ux = p1[0]-p0[0], uy = p1[1]-p0[1], uz = p1[2]-p0[2];
-  float vx = p2[0]-p0[0], vy = p2[1]-p0[1], vz = p2[2]-p0[2];
-  float nx = uy*vz - uz*vy, ny = uz*vx - ux*vz, nz = ux*vy - uy*vx;
-  float len = sqrtf(nx*nx + ny*ny + nz*nz);
-  if (len <= 0.0f) {
-    // zero plane: accumulating it adds exact +0 products, bitwise
-    // identical to the oracle's skip (quadric sums are never -0)
-    fq[t] = SimpPlane{0.0f, 0.0f, 0.0f, 0.0f};
-    fvalid[t] = 0;
-    return;
-  }
-  float inv = 1.0f / len;
-  nx *= inv; ny *= inv; nz *= inv;
-  float d = -(nx*p0[0] + ny*p0[1] + nz*p0[2]);
-  fq[t] = SimpPlane{nx, ny, nz, d};
-  fvalid[t] = 1;
+  SimpPlane p = sq_face_plane(verts, faces_g[3*t], faces_g[3*t+1],
+                              faces_g[3*t+2]);
+  fq[t] = p;
+  fvalid[t] = (p.nx != 0.0f || p.ny != 0.0f || p.nz != 0.0f) ? 1 : 0;
 }
 
 // [S2] emit (vertex, face) pairs for quadric accumulation; inactive
@@ -189,50 +336,10 @@ __global__ void k_edge_pick(const uint32_t *__restrict__ faces_g,
   if (t >= ntris) return;
   uint32_t lab = flab[t];
   if (!active_lab[lab]) return;
-  const uint32_t vb = vbase[lab];
-  // stage the 3 corner quadrics + positions in registers once per face
-  // (the a<b swap below defeats CSE of the Q loads otherwise)
   uint32_t fc[3] = {faces_g[3*t], faces_g[3*t+1], faces_g[3*t+2]};
   float cq[3][10], cp[3][3];
-  #pragma unroll
-  for (int ci = 0; ci < 3; ++ci) {
-    const float4 *qp = (const float4 *)(Q + 12ull*fc[ci]);
-    float4 a = qp[0], b = qp[1], cc = qp[2];
-    cq[ci][0] = a.x; cq[ci][1] = a.y; cq[ci][2] = a.z; cq[ci][3] = a.w;
-    cq[ci][4] = b.x; cq[ci][5] = b.y; cq[ci][6] = b.z; cq[ci][7] = b.w;
-    cq[ci][8] = cc.x; cq[ci][9] = cc.y;
-    #pragma unroll
-    for (int k = 0; k < 3; ++k) cp[ci][k] = verts[3ull*fc[ci] + k];
-  }
-  #pragma unroll
-  for (int e = 0; e < 3; ++e) {
-    const int ea = e, eb = (e + 1) % 3;   // compile-time after unroll
-    uint32_t a = fc[ea], b = fc[eb];
-    if (a == b) continue;
-    // canonical u < w; addition is commutative-safe here only because
-    // both operand orders are evaluated identically (x+y) — keep the
-    // oracle's Q[u]+Q[w] order via selects on compile-time indices
-    bool fwd = a < b;
-    uint32_t u = fwd ? a : b, w = fwd ? b : a;
-    float mx = 0.5f*((fwd ? cp[ea][0] : cp[eb][0]) + (fwd ? cp[eb][0] : cp[ea][0]));
-    float my = 0.5f*((fwd ? cp[ea][1] : cp[eb][1]) + (fwd ? cp[eb][1] : cp[ea][1]));
-    float mz = 0.5f*((fwd ? cp[ea][2] : cp[eb][2]) + (fwd ? cp[eb][2] : cp[ea][2]));
-    float S[10];
-    #pragma unroll
-    for (int k = 0; k < 10; ++k)
-      S[k] = (fwd ? cq[ea][k] : cq[eb][k]) + (fwd ? cq[eb][k] : cq[ea][k]);
-    float cost = sq_place_cost(S, mx, my, mz);
-    if (cost > max_cost) continue;
-    uint32_t cb = __float_as_uint(cost);
-    // per-edge tie jitter — identical to oracle/simplify.c, which works
-    // in label-LOCAL vertex ids: subtract the label's vertex base
-    uint32_t ul = u - vb, wl = w - vb;
-    uint32_t hsh = ul ^ (wl * 2654435761u);
-    hsh ^= hsh >> 16; hsh *= 2246822519u; hsh ^= hsh >> 13;
-    cb ^= (hsh & 7u);
-    atomicMin(&pick[u], ((unsigned long long)cb << 32) | w);
-    atomicMin(&pick[w], ((unsigned long long)cb << 32) | u);
-  }
+  sq_stage_corners(fc, verts, Q, cq, cp);
+  sq_edge_bids(fc, cq, cp, pick, 0u, vbase[lab], max_cost);
 }
 
 // [S5] matched pairs collapse; u (smaller id) survives. Matched
@@ -251,20 +358,7 @@ __global__ void k_collapse(unsigned long long *__restrict__ pick,
   if (w <= u) return;
   unsigned long long pw = pick[w];
   if (pw == ~0ull || (uint32_t)pw != u) return;
-  {
-    float mx = 0.5f*(verts[3*u]+verts[3*w]);
-    float my = 0.5f*(verts[3*u+1]+verts[3*w+1]);
-    float mz = 0.5f*(verts[3*u+2]+verts[3*w+2]);
-    float S[10];
-    #pragma unroll
-    for (int k = 0; k < 10; ++k)
-      S[k] = Q[12*u + k] + Q[12*(uint64_t)w + k];
-    float px, py, pz;
-    (void)sq_place(S, mx, my, mz, &px, &py, &pz);
-    verts[3*u] = px; verts[3*u+1] = py; verts[3*u+2] = pz;
-  }
-  #pragma unroll
-  for (int k = 0; k < 10; ++k) Q[12*u + k] += Q[12*(uint64_t)w + k];
+  sq_collapse(verts, Q, u, w);
   remap[w] = (uint32_t)u;
   pick[u] = ~0ull;
   pick[w] = ~0ull;
@@ -301,20 +395,7 @@ __global__ void k_accept(const unsigned long long *__restrict__ pick,
   if (pw == ~0ull) return;             // matched or pickless
   if ((uint32_t)pw > w) return;        // proposers never accept
   uint64_t u = (uint64_t)aw - 1;
-  {
-    float mx = 0.5f*(verts[3*u]+verts[3*w]);
-    float my = 0.5f*(verts[3*u+1]+verts[3*w+1]);
-    float mz = 0.5f*(verts[3*u+2]+verts[3*w+2]);
-    float S[10];
-    #pragma unroll
-    for (int k = 0; k < 10; ++k)
-      S[k] = Q[12*u + k] + Q[12*(uint64_t)w + k];
-    float px, py, pz;
-    (void)sq_place(S, mx, my, mz, &px, &py, &pz);
-    verts[3*u] = px; verts[3*u+1] = py; verts[3*u+2] = pz;
-  }
-  #pragma unroll
-  for (int k = 0; k < 10; ++k) Q[12*u + k] += Q[12*(uint64_t)w + k];
+  sq_collapse(verts, Q, u, w);
   remap[w] = (uint32_t)u;
 }
 
@@ -542,6 +623,14 @@ __global__ void k_gather_final(const uint32_t *__restrict__ park_faces,
 // the sorted CSR, jittered pick encoding on label-local ids, mutual-pick
 // matched collapse, stable compaction, same termination conditions).
 
+// labels up to SIMP_BIG_CAP faces simplify entirely inside one workgroup
+// each (cache-resident round loop, no global sorts); only bigger labels
+// go through the global-rounds machinery.
+#define SIMP_BIG_CAP 65536u
+// threads per label workgroup: the kernel's launch bounds and strides and
+// the host's block dimension (6/256 won the SUBS x BS sweeps)
+constexpr int SIMP_LABEL_BS = 256;
+
 // wave-shuffle prefix machinery shared by the block-wide helpers below:
 // each thread sums its contiguous chunk, a 64-lane shuffle scan orders
 // the per-thread partials within the wave (no LDS), ONE barrier shares
@@ -607,24 +696,24 @@ __device__ uint32_t blk_exscan(const uint32_t *src, uint32_t *dst,
 // the (cheap, LDS) rm gathers instead of paying a 12 B/face global
 // write + re-read. Identical output order to the old rewrite + compact
 // pair.
-template <int BS, int MAXN, typename RMT>
+template <int BS>
 __device__ uint32_t blk_rewrite_compact(const uint32_t *__restrict__ fa,
                                         uint32_t *__restrict__ fb,
-                                        const RMT *__restrict__ rm,
+                                        const uint32_t *__restrict__ rm,
                                         uint32_t v0,
                                         uint32_t n, uint32_t *s_sums) {
   const uint32_t tid = threadIdx.x;
   const uint32_t chunk = (n + BS - 1) / BS;
   const uint32_t lo = tid * chunk;
   const uint32_t hi = lo + chunk < n ? lo + chunk : n;
-  // bitmask register array sized for the band's face-count cap MAXN
-  constexpr uint32_t MAXW = ((uint32_t)MAXN / BS + 63) / 64 + 1;
+  // bitmask register array sized for the kernel's face-count cap
+  constexpr uint32_t MAXW = (SIMP_BIG_CAP / BS + 63) / 64 + 1;
   unsigned long long bm[MAXW] = {};
   uint32_t sum = 0;
   for (uint32_t i = lo; i < hi; ++i) {
-    uint32_t i0 = (uint32_t)rm[fa[3*i] - v0];
-    uint32_t i1 = (uint32_t)rm[fa[3*i+1] - v0];
-    uint32_t i2 = (uint32_t)rm[fa[3*i+2] - v0];
+    uint32_t i0 = rm[fa[3*i] - v0];
+    uint32_t i1 = rm[fa[3*i+1] - v0];
+    uint32_t i2 = rm[fa[3*i+2] - v0];
     if (i0 != i1 && i1 != i2 && i0 != i2) {
       bm[(i - lo) >> 6] |= 1ull << ((i - lo) & 63);
       ++sum;
@@ -634,33 +723,40 @@ __device__ uint32_t blk_rewrite_compact(const uint32_t *__restrict__ fa,
   uint32_t run = blk_prefix<BS>(sum, s_sums, &total);
   for (uint32_t i = lo; i < hi; ++i)
     if (bm[(i - lo) >> 6] & (1ull << ((i - lo) & 63))) {
-      fb[3*run] = v0 + (uint32_t)rm[fa[3*i] - v0];
-      fb[3*run+1] = v0 + (uint32_t)rm[fa[3*i+1] - v0];
-      fb[3*run+2] = v0 + (uint32_t)rm[fa[3*i+2] - v0];
+      fb[3*run] = v0 + rm[fa[3*i] - v0];
+      fb[3*run+1] = v0 + rm[fa[3*i+1] - v0];
+      fb[3*run+2] = v0 + rm[fa[3*i+2] - v0];
       ++run;
     }
   __syncthreads();  // s_sums reusable after this
   return total;
 }
 
-// (an amdgpu_waves_per_eu(4) floor was measured here: it fits 127 VGPRs
-// with 52 B/lane scratch, and the spill traffic LOSES 7% net — the
-// natural 148-VGPR / 3-waves-per-SIMD allocation stands)
-// The 16-wide bitonic sort tier is the kernel's VGPR peak: with it the
-// allocation is 148 VGPRs (3 waves/SIMD), without it 116 (4 waves/SIMD)
-// — degree>8 vertices are rare enough that the insertion-sort fallback
-// plus the extra wave slot wins (A/B'd on the 512^3/50k config).
-#ifndef SIMP_D16_TIER
-#define SIMP_D16_TIER 1
-#endif
-// WAVEMODE (BS=64, one wave per label): the whole round loop runs
-// wave-synchronously — every __syncthreads() in a 64-thread block
-// lowers to a waitcnt, the pick table ALIASES the (phase-disjoint)
-// degree/cursor array, and remap is u16 — 20 KB LDS per label instead
-// of 33, so ~7 labels are resident per CU instead of 3. Owns the
-// (nt_lo, nt_hi] x (nv_lo, nv_hi] band its launch names.
-template <bool CLLDS, int BS, int CAPVT, bool WAVEMODE = false>
-__global__ __launch_bounds__(BS)
+// pick/remap/accept reset of one label-local vertex slot
+__device__ __forceinline__ void simp_reset_vertex(unsigned long long *pick_l,
+                                                  uint32_t *rm,
+                                                  uint32_t *accept_l,
+                                                  uint32_t v,
+                                                  uint32_t propose) {
+  pick_l[v] = ~0ull;
+  rm[v] = v;  // remap identity (consumed in collapse)
+  if (propose) accept_l[v] = 0xFFFFFFFFu;
+}
+
+// CAPV = LDS vertex capacity: a label with nv <= CAPV keeps its degree,
+// pick and remap tables in LDS, a bigger one in its global slices.
+// amdgpu_waves_per_eu(4) IS applied, as a floor of 4 waves per SIMD. The
+// CAPV=2048 instantiation meets it: 128 VGPRs, 48 B/lane of scratch (the
+// keep bitmask and a few spills; the 16-wide sort tier is the VGPR peak).
+// The floor lost 7% while it spilled 52 B/lane from a 148-VGPR kernel and
+// was adopted once the kernel fit (simplifier journey and the
+// cleanup's resource table). The CAPV=4096 instantiation cannot meet the
+// floor — its 64 KB of LDS allows 2 blocks per CU = 2 waves per SIMD — so
+// the compiler warns "desired occupancy was 4, final occupancy is 2" for
+// it; that is LDS-bound and expected, and it keeps its natural
+// spill-free 151-VGPR allocation.
+template <int CAPV>
+__global__ __launch_bounds__(SIMP_LABEL_BS)
 __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
     uint32_t *__restrict__ faces_g,       // slices at 3*tri_off[b]
     uint32_t *__restrict__ faces_tmp,     // same slicing (scratch)
@@ -674,7 +770,6 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
     uint32_t *__restrict__ adj_off,       // per vertex
     uint32_t *__restrict__ cols,          // 3 per face slot (CSR payload)
     SimpPlane *__restrict__ fq,           // per face (round scratch)
-    uint8_t *__restrict__ fvalid,         // per face (plane valid / keep)
     uint32_t *__restrict__ nt_cur,
     const uint32_t *__restrict__ target,
     uint8_t *__restrict__ active,
@@ -683,15 +778,11 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
     uint32_t *__restrict__ roundhist,  // 160 u32 or null (see host)
     float max_cost, uint32_t nlabels, uint32_t big_cap,
     uint32_t subs, uint32_t nv_lo, uint32_t nv_hi,
-    uint32_t nt_lo, uint32_t nt_hi,
     uint32_t *__restrict__ accept_g,  // per-vertex (wave 2)
-    uint32_t propose,
-    const uint32_t *__restrict__ sched /*block->label, largest first*/) {
-  if (blockIdx.x >= nlabels) return;
-  // biggest-label-first dispatch: per-label serial time scales with nt0,
-  // and a 65k-face label dispatched late extends the whole launch by its
-  // full runtime — schedule stragglers first so they overlap the swarm
-  const uint32_t b = sched ? sched[blockIdx.x] : blockIdx.x;
+    uint32_t propose) {
+  constexpr int BS = SIMP_LABEL_BS;
+  const uint32_t b = blockIdx.x;  // one workgroup per label
+  if (b >= nlabels) return;
   unsigned long long t_start =
       roundhist ? __builtin_amdgcn_s_memtime() : 0;
   const uint32_t f0 = tri_off[b];
@@ -699,10 +790,8 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
   if (nt0 > big_cap) return;  // global-rounds path handles big labels
   const uint32_t v0 = vbase[b];
   const uint32_t nv = vbase[b + 1] - v0;
-  // size-class dispatch: each launch variant owns an (nv_lo, nv_hi] x
-  // (nt_lo, nt_hi] band
+  // size-class dispatch: each launch owns an (nv_lo, nv_hi] band
   if (nv <= nv_lo || nv > nv_hi) return;
-  if (nt0 <= nt_lo || nt0 > nt_hi) return;
   if (!active[b]) {
     // already at/below target: final faces = original faces; park them
     for (uint32_t i = threadIdx.x; i < 3 * nt0; i += BS)
@@ -723,34 +812,20 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
   // neighboring faces' vertices share cache lines, so the global
   // atomicAdd/atomicMin streams serialize on hot L2 lines — LDS atomics
   // are bank-parallel. (~25 KB -> ~6 blocks/CU.)
-  constexpr uint32_t CAPV = CAPVT;
-  __shared__ uint32_t s_deg[WAVEMODE ? 1 : CAPV];
+  __shared__ uint32_t s_deg[CAPV];
   __shared__ unsigned long long s_pick[CAPV];
-  // optional LDS-resident CSR payload (face ids, u16) for rounds whose
-  // face count fits; costs 24 KB LDS -> fewer blocks/CU. The host only
-  // launches CLLDS=false (measured-and-rejected).
-  constexpr uint32_t CAPF = CLLDS ? 4096u : 1u;
-  __shared__ uint16_t s_cl[3 * CAPF];
   // remap holds label-LOCAL canonical ids; LDS-resident when the label
-  // fits (rewrite's 3 gathers/face are the hot readers). WAVEMODE packs
-  // it to u16 (label-local ids < CAPV).
-  using RMT = typename std::conditional<WAVEMODE, uint16_t,
-                                        uint32_t>::type;
-  __shared__ RMT s_remap[CAPV];
-  const bool lds_mode = (nv <= CAPV);
-  // WAVEMODE: the degree/cursor array lives in the PICK bytes — deg is
-  // dead before the first pick write of each group (the reset pass
-  // below runs after the last cursor read, behind a barrier)
-  uint32_t *dg = WAVEMODE ? (uint32_t *)s_pick
-                          : (lds_mode ? s_deg : (deg + v0));
+  // fits (rewrite's 3 gathers/face are the hot readers)
+  __shared__ uint32_t s_remap[CAPV];
+  const bool lds_mode = (nv <= (uint32_t)CAPV);
+  uint32_t *dg = lds_mode ? s_deg : (deg + v0);
   unsigned long long *pick_l =
       lds_mode ? s_pick : (pick + v0);
-  RMT *rm = lds_mode ? s_remap : (RMT *)(remap + v0);
+  uint32_t *rm = lds_mode ? s_remap : (remap + v0);
   // accept table (proposal wave): u32 id-only keys — lives in the
   // degree array's bytes (dead during the collapse phases) when the
   // label is LDS-resident; global fallback otherwise
-  uint32_t *accept_l = (!WAVEMODE && lds_mode)
-                           ? s_deg : (accept_g + v0);
+  uint32_t *accept_l = lds_mode ? s_deg : (accept_g + v0);
   // ping-pong face buffers: rewrite reads fa, compaction scatters into
   // fb, then the buffers swap — no copy-back pass. Parking at the end
   // reads whichever buffer is current.
@@ -774,7 +849,6 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
     if (nt <= tgt) break;
     ++n_groups;
     const uint32_t nt_group = nt;  // group-progress watermark
-    const bool clmode = CLLDS && (nt <= CAPF);
     PHASE_MARK(0)  // loop head
 
     // [1+2] face planes fused with the CSR degree count (one face pass)
@@ -785,37 +859,16 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
       atomicAdd(&dg[i0 - v0], 1u);
       atomicAdd(&dg[i1 - v0], 1u);
       atomicAdd(&dg[i2 - v0], 1u);
-      const float *p0 = verts + 3ull*i0, *p1 = verts + 3ull*i1,
-                  *p2 = verts + 3ull*i2;
-      float ux = p1[0]-p0[0], uy = p1[1]-p0[1], uz = p1[2]-p0[2];
-      float vx = p2[0]-p0[0], vy = p2[1]-p0[1], vz = p2[2]-p0[2];
-      float nx = uy*vz - uz*vy, ny = uz*vx - ux*vz, nz = ux*vy - uy*vx;
-      float len = sqrtf(nx*nx + ny*ny + nz*nz);
-      if (len <= 0.0f) {
-        pl[f] = SimpPlane{0.0f, 0.0f, 0.0f, 0.0f};  // +0 products = skip
-        continue;
-      }
-      float inv = 1.0f / len;
-      nx *= inv; ny *= inv; nz *= inv;
-      float d = -(nx*p0[0] + ny*p0[1] + nz*p0[2]);
-      pl[f] = SimpPlane{nx, ny, nz, d};
+      pl[f] = sq_face_plane(verts, i0, i1, i2);
     }
     __syncthreads();
     PHASE_MARK(1)  // planes + degree count
     // [3] offsets; the scan also writes the fill cursors (dst2 = dg)
     blk_exscan<BS>(dg, aoff, nv, 0, s_sums, dg);
-    if (clmode) {
-      for (uint32_t f = tid; f < nt; f += BS) {
-        s_cl[atomicAdd(&dg[fa[3*f] - v0], 1u)] = (uint16_t)f;
-        s_cl[atomicAdd(&dg[fa[3*f+1] - v0], 1u)] = (uint16_t)f;
-        s_cl[atomicAdd(&dg[fa[3*f+2] - v0], 1u)] = (uint16_t)f;
-      }
-    } else {
-      for (uint32_t f = tid; f < nt; f += BS) {
-        cl[atomicAdd(&dg[fa[3*f] - v0], 1u)] = f;
-        cl[atomicAdd(&dg[fa[3*f+1] - v0], 1u)] = f;
-        cl[atomicAdd(&dg[fa[3*f+2] - v0], 1u)] = f;
-      }
+    for (uint32_t f = tid; f < nt; f += BS) {
+      cl[atomicAdd(&dg[fa[3*f] - v0], 1u)] = f;
+      cl[atomicAdd(&dg[fa[3*f+1] - v0], 1u)] = f;
+      cl[atomicAdd(&dg[fa[3*f+2] - v0], 1u)] = f;
     }
     __syncthreads();
     PHASE_MARK(2)  // offsets scan + CSR fill
@@ -829,96 +882,13 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
       #pragma unroll
       for (int k = 0; k < 10; ++k) q[k] = 0.0f;
       if (d <= 8) {
-        // dominant tier: interior vertices have degree ~6 — an 8-wide
-        // bitonic network + 8 plane gathers costs ~1/3 of the 16-wide
-        // path it replaces. Sorted order is unique (face ids distinct),
-        // so this matches the oracle's insertion sort exactly.
-        uint32_t fl[8];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k)
-          fl[k] = (k < (int)d)
-                      ? (clmode ? (uint32_t)s_cl[lo + k] : cl[lo + k])
-                      : 0xFFFFFFFFu;
-        #pragma unroll
-        for (int ksz = 2; ksz <= 8; ksz <<= 1) {
-          #pragma unroll
-          for (int j = ksz >> 1; j > 0; j >>= 1) {
-            #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              int l = i ^ j;
-              if (l > i) {
-                bool up = ((i & ksz) == 0);
-                uint32_t a = fl[i], b2 = fl[l];
-                bool sw = up ? (a > b2) : (a < b2);
-                fl[i] = sw ? b2 : a;
-                fl[l] = sw ? a : b2;
-              }
-            }
-          }
-        }
-        SimpPlane ps[8];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k)
-          ps[k] = pl[k < (int)d ? fl[k] : 0u];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k)
-          if (k < (int)d)
-            sq_add_plane(q, ps[k].nx, ps[k].ny, ps[k].nz, ps[k].d, 1.0f);
-      } else if (SIMP_D16_TIER && d <= 16) {
-        // register path: one batched load of the face list, bitonic
-        // sort network (compile-time indices, no global RMW chains).
-        uint32_t fl[16];
-        #pragma unroll
-        for (int k = 0; k < 16; ++k)
-          fl[k] = (k < (int)d)
-                      ? (clmode ? (uint32_t)s_cl[lo + k] : cl[lo + k])
-                      : 0xFFFFFFFFu;
-        #pragma unroll
-        for (int ksz = 2; ksz <= 16; ksz <<= 1) {
-          #pragma unroll
-          for (int j = ksz >> 1; j > 0; j >>= 1) {
-            #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              int l = i ^ j;
-              if (l > i) {
-                bool up = ((i & ksz) == 0);
-                uint32_t a = fl[i], b2 = fl[l];
-                bool sw = up ? (a > b2) : (a < b2);
-                fl[i] = sw ? b2 : a;
-                fl[l] = sw ? a : b2;
-              }
-            }
-          }
-        }
-        // gather planes in two 8-batches (8 independent loads in flight
-        // each) — staging all 16 at once cost 64 VGPRs and pushed the
-        // kernel past the 128-VGPR / 4-waves-per-SIMD occupancy step.
-        // Accumulation order (ascending fl) is unchanged.
-        #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          SimpPlane ps[8];
-          #pragma unroll
-          for (int k = 0; k < 8; ++k)
-            // pad with face 0 (nt >= 1 inside the loop); fl[k] is the
-            // 0xFFFFFFFF sort sentinel beyond d, must not be indexed
-            ps[k] = pl[8*h + k < (int)d ? fl[8*h + k] : 0u];
-          #pragma unroll
-          for (int k = 0; k < 8; ++k)
-            if (8*h + k < (int)d)
-              sq_add_plane(q, ps[k].nx, ps[k].ny, ps[k].nz, ps[k].d, 1.0f);
-        }
-      } else if (clmode) {
-        for (uint32_t i = lo + 1; i < hi; ++i) {
-          uint16_t x = s_cl[i];
-          uint32_t j = i;
-          while (j > lo && s_cl[j-1] > x) { s_cl[j] = s_cl[j-1]; --j; }
-          s_cl[j] = x;
-        }
-        for (uint32_t i = lo; i < hi; ++i) {
-          SimpPlane p = pl[s_cl[i]];
-          sq_add_plane(q, p.nx, p.ny, p.nz, p.d, 1.0f);
-        }
+        // dominant tier: interior vertices have degree ~6 — the 8-wide
+        // network + 8 plane gathers costs ~1/3 of the 16-wide one
+        sq_sort_accum<8>(q, cl + lo, d, pl);
+      } else if (d <= 16) {
+        sq_sort_accum<16>(q, cl + lo, d, pl);
       } else {
+        // rare high-degree vertex: the oracle's insertion sort in place
         for (uint32_t i = lo + 1; i < hi; ++i) {
           uint32_t x = cl[i];
           uint32_t j = i;
@@ -936,23 +906,10 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
         qo[1] = make_float4(q[4], q[5], q[6], q[7]);
         qo[2] = make_float4(q[8], q[9], 0.0f, 0.0f);
       }
-      if (!WAVEMODE) {
-        pick_l[v] = ~0ull;  // fused pick reset (same-thread slot)
-        rm[v] = (RMT)v;     // fused remap identity (consumed in collapse)
-        if (propose) accept_l[v] = 0xFFFFFFFFu;
-      }
+      // fused reset (same-thread slots; dg's last read was above)
+      simp_reset_vertex(pick_l, rm, accept_l, v, propose);
     }
     __syncthreads();
-    if (WAVEMODE) {
-      // dg (aliasing the pick bytes) had its last read above; now the
-      // pick table takes the space back
-      for (uint32_t v = tid; v < nv; v += BS) {
-        pick_l[v] = ~0ull;
-        rm[v] = (RMT)v;
-        if (propose) accept_l[v] = 0xFFFFFFFFu;
-      }
-      __syncthreads();
-    }
     PHASE_MARK(3)  // sort + quadric accumulate
     // sub-rounds: reuse merged quadrics (Q[u] += Q[w] on collapse) for
     // up to `subs` pick/collapse/compact passes per recompute (oracle
@@ -962,57 +919,16 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
     if (nt <= tgt) break;
     ++n_subs;
     if (sub > 0) {
-      for (uint32_t v = tid; v < nv; v += BS) {
-        pick_l[v] = ~0ull;
-        rm[v] = (RMT)v;
-        if (propose) accept_l[v] = 0xFFFFFFFFu;
-      }
+      for (uint32_t v = tid; v < nv; v += BS)
+        simp_reset_vertex(pick_l, rm, accept_l, v, propose);
       __syncthreads();
     }
-    // [6] picks (oracle step 2). Q rows are 12 floats (48 B, 16-B
-    // aligned): stage each corner's quadric ONCE per face (3 dwordx4
-    // loads) and build every edge's sum from registers — the edge loop
-    // re-loading both quadrics per edge doubled the phase's traffic.
-    // f32 order preserved via selects on compile-time indices, exactly
-    // like the global k_edge_pick.
+    // [6] picks (oracle step 2)
     for (uint32_t f = tid; f < nt; f += BS) {
       uint32_t fc[3] = {fa[3*f], fa[3*f+1], fa[3*f+2]};
       float cq[3][10], cp[3][3];
-      #pragma unroll
-      for (int ci = 0; ci < 3; ++ci) {
-        const float4 *qp = (const float4 *)(Q + 12ull*fc[ci]);
-        float4 a4 = qp[0], b4 = qp[1], c4 = qp[2];
-        cq[ci][0] = a4.x; cq[ci][1] = a4.y; cq[ci][2] = a4.z;
-        cq[ci][3] = a4.w; cq[ci][4] = b4.x; cq[ci][5] = b4.y;
-        cq[ci][6] = b4.z; cq[ci][7] = b4.w; cq[ci][8] = c4.x;
-        cq[ci][9] = c4.y;
-        #pragma unroll
-        for (int k = 0; k < 3; ++k) cp[ci][k] = verts[3ull*fc[ci] + k];
-      }
-      #pragma unroll
-      for (int e = 0; e < 3; ++e) {
-        const int ea = e, eb = (e + 1) % 3;  // compile-time after unroll
-        uint32_t a = fc[ea], bb = fc[eb];
-        if (a == bb) continue;
-        bool fwd = a < bb;
-        uint32_t u = fwd ? a : bb, w = fwd ? bb : a;
-        float mx = 0.5f*((fwd ? cp[ea][0] : cp[eb][0]) + (fwd ? cp[eb][0] : cp[ea][0]));
-        float my = 0.5f*((fwd ? cp[ea][1] : cp[eb][1]) + (fwd ? cp[eb][1] : cp[ea][1]));
-        float mz = 0.5f*((fwd ? cp[ea][2] : cp[eb][2]) + (fwd ? cp[eb][2] : cp[ea][2]));
-        float S[10];
-        #pragma unroll
-        for (int k = 0; k < 10; ++k)
-          S[k] = (fwd ? cq[ea][k] : cq[eb][k]) + (fwd ? cq[eb][k] : cq[ea][k]);
-        float cost = sq_place_cost(S, mx, my, mz);
-        if (cost > max_cost) continue;
-        uint32_t cb = __float_as_uint(cost);
-        uint32_t ul = u - v0, wl = w - v0;  // label-local ids (oracle)
-        uint32_t hsh = ul ^ (wl * 2654435761u);
-        hsh ^= hsh >> 16; hsh *= 2246822519u; hsh ^= hsh >> 13;
-        cb ^= (hsh & 7u);
-        atomicMin(&pick_l[ul], ((unsigned long long)cb << 32) | w);
-        atomicMin(&pick_l[wl], ((unsigned long long)cb << 32) | u);
-      }
+      sq_stage_corners(fc, verts, Q, cq, cp);
+      sq_edge_bids(fc, cq, cp, pick_l, v0, v0, max_cost);
     }
     PHASE_MARK(4)  // edge picks
     // [7] matched-pair collapse (oracle step 3); rm was pre-set to the
@@ -1027,20 +943,7 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
       if (w <= u) continue;
       unsigned long long pw = pick_l[w - v0];
       if (pw == ~0ull || (uint32_t)pw != u) continue;
-      {
-        float mx = 0.5f*(verts[3ull*u]+verts[3ull*w]);
-        float my = 0.5f*(verts[3ull*u+1]+verts[3ull*w+1]);
-        float mz = 0.5f*(verts[3ull*u+2]+verts[3ull*w+2]);
-        float S[10];
-        #pragma unroll
-        for (int k = 0; k < 10; ++k)
-          S[k] = Q[12ull*u + k] + Q[12ull*w + k];
-        float px, py, pz;
-        (void)sq_place(S, mx, my, mz, &px, &py, &pz);
-        verts[3ull*u] = px; verts[3ull*u+1] = py; verts[3ull*u+2] = pz;
-      }
-      #pragma unroll
-      for (int k = 0; k < 10; ++k) Q[12ull*u + k] += Q[12ull*w + k];
+      sq_collapse(verts, Q, u, w);
       rm[w - v0] = u - v0;
       // blocked marking: matched vertices leave the pick graph (the
       // races on these plain stores are benign: any reader's decision
@@ -1073,29 +976,15 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
         if ((uint32_t)pw > w) continue;       // proposers never accept
         uint32_t ul = aw - 1;
         uint32_t u = v0 + ul;
-        {
-          float mx = 0.5f*(verts[3ull*u]+verts[3ull*w]);
-          float my = 0.5f*(verts[3ull*u+1]+verts[3ull*w+1]);
-          float mz = 0.5f*(verts[3ull*u+2]+verts[3ull*w+2]);
-          float S[10];
-          #pragma unroll
-          for (int k = 0; k < 10; ++k)
-            S[k] = Q[12ull*u + k] + Q[12ull*w + k];
-          float px, py, pz;
-          (void)sq_place(S, mx, my, mz, &px, &py, &pz);
-          verts[3ull*u] = px; verts[3ull*u+1] = py; verts[3ull*u+2] = pz;
-        }
-        #pragma unroll
-        for (int k = 0; k < 10; ++k) Q[12ull*u + k] += Q[12ull*w + k];
-        rm[v] = (RMT)ul;
+        sq_collapse(verts, Q, u, w);
+        rm[v] = ul;
         atomicAdd(&s_collapses, 1u);
       }
       __syncthreads();
     }
     if (s_collapses == 0) break;
     // [8] fused rewrite + stable compact (oracle step 4)
-    uint32_t kept = blk_rewrite_compact<BS, WAVEMODE ? 8192 : 65536, RMT>(
-        fa, fb, rm, v0, nt, s_sums);
+    uint32_t kept = blk_rewrite_compact<BS>(fa, fb, rm, v0, nt, s_sums);
     { uint32_t *t = fa; fa = fb; fb = t; }  // compacted faces now in fa
     if (tid == 0) s_nt = kept;
     __syncthreads();

@@ -19,12 +19,13 @@
 //       per voxel, in place;
 //       (optional, mg_mesh_chunk_filled) fill_holes.hip: hole filling by
 //       union-find rounds, hole volume kept resident for mg_mesh_holes
-//   [1] k_count        wave-per-64-cell-segment triangle counts
+//   [1] k_count        wave-per-64-cell-segment triangle counts: one
+//                      classification per cell, one trip per label
 //                      (+ label hash build)                    -> segcnt
 //   [2] scan           rocPRIM exclusive scan                  -> segoff, T
-//   [3] k_emit         recompute counts, wave prefix, write one 16-B
-//                      record (3 weld slots + label id) per triangle in
-//                      canonical global order (case tables in LDS)
+//   [3] k_emit         classify again, wave prefix, write one 8-B
+//                      record + 4-B label id per triangle in canonical
+//                      global order (count table in LDS)
 //   [4] partition      rocPRIM stable radix-sort by label id + 16-B gather
 //   [5] weld           direct-addressed (edge,side) table: atomicMax(~pos)
 //                      first-seen positions (LDS pre-dedup), bit-packed
@@ -316,26 +317,64 @@ __device__ __forceinline__ void load_corners(const T *__restrict__ labels,
   c[6] = p[sxy + sx];     c[7] = p[sxy + sx + 1];
 }
 
-template <typename T>
-__device__ __forceinline__ uint32_t cell_tri_count(const T c[8],
-                                                   const uint8_t *cnt_tab) {
-  if (c[0] == c[1] && c[0] == c[2] && c[0] == c[3] && c[0] == c[4] &&
-      c[0] == c[5] && c[0] == c[6] && c[0] == c[7])
-    return 0;
-  uint32_t total = 0;
-  #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    T L = c[i];
-    if (L == 0) continue;
-    bool seen = false;
-    for (int j = 0; j < i; ++j) seen |= (c[j] == L);
-    if (seen) continue;
-    unsigned mask = 0;
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) mask |= (c[j] == L) ? (1u << j) : 0u;
-    total += cnt_tab[mask];
+// One classification per cell. The 28 pairwise corner compares are each
+// done once and give
+//   rows   byte i = the 8-bit mask of corners equal to c[i], which is the
+//          MC case mask of the label at corner i
+//   first  bit i set when c[i] != 0 and no lower corner equals it: the
+//          cell's distinct non-zero labels, ascending i = first-seen corner
+//          order. 0 for a uniform cell. In a non-uniform cell every such
+//          label has triangles (only masks 0 and 255 have none,
+//          tests/test_mc_table.py).
+// Count and emit walk `first` lowest bit first, so a wave makes as many
+// trips as its busiest lane has labels, not 8.
+struct CellClass {
+  uint64_t rows;
+  uint32_t first;
+  __device__ __forceinline__ uint32_t row(uint32_t i) const {
+    return (uint32_t)(rows >> (i * 8u)) & 255u;
   }
-  return total;
+};
+
+template <typename T>
+__device__ __forceinline__ CellClass classify_cell(const T c[8]) {
+  // one byte-wide register per row while the compares run: every select
+  // then takes a constant below 256 (packed rows would keep some forty
+  // 32-bit literals in registers across the segment loop)
+  uint32_t r[8];
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = 1u << i;  // a corner equals itself
+  uint32_t seen = 0;
+  #pragma unroll
+  for (int j = 1; j < 8; ++j) {
+    #pragma unroll
+    for (int i = 0; i < j; ++i) {
+      const bool eq = c[i] == c[j];
+      r[i] |= eq ? (1u << j) : 0u;
+      r[j] |= eq ? (1u << i) : 0u;
+      seen |= eq ? (1u << j) : 0u;
+    }
+  }
+  uint32_t nz = 0;
+  #pragma unroll
+  for (int i = 0; i < 8; ++i) nz |= (c[i] != 0) ? (1u << i) : 0u;
+  const uint32_t lo = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24);
+  const uint32_t hi = r[4] | (r[5] << 8) | (r[6] << 16) | (r[7] << 24);
+  CellClass k;
+  k.rows = ((uint64_t)hi << 32) | lo;
+  k.first = r[0] == 255u ? 0u : (nz & ~seen);
+  return k;
+}
+
+// c[i] for a per-lane i, by selects (a dynamically indexed array would
+// live in scratch)
+template <typename T>
+__device__ __forceinline__ T pick_corner(const T c[8], uint32_t i) {
+  const bool b0 = i & 1u, b1 = i & 2u, b2 = i & 4u;
+  const T a0 = b0 ? c[1] : c[0], a1 = b0 ? c[3] : c[2];
+  const T a2 = b0 ? c[5] : c[4], a3 = b0 ? c[7] : c[6];
+  const T d0 = b1 ? a1 : a0, d1 = b1 ? a3 : a2;
+  return b2 ? d1 : d0;
 }
 
 struct GridDims {
@@ -391,24 +430,11 @@ __global__ void k_count(const T *__restrict__ labels, GridDims g,
     if (cx < g.ncx) {
       T c[8];
       load_corners(labels, g.sx, sxy, cx, cy, cz, c);
-      if (!(c[0] == c[1] && c[0] == c[2] && c[0] == c[3] && c[0] == c[4] &&
-            c[0] == c[5] && c[0] == c[6] && c[0] == c[7])) {
-        #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          T L = c[i];
-          if (L == 0) continue;
-          bool seen = false;
-          for (int j = 0; j < i; ++j) seen |= (c[j] == L);
-          if (seen) continue;
-          unsigned mask = 0;
-          #pragma unroll
-          for (int j = 0; j < 8; ++j) mask |= (c[j] == L) ? (1u << j) : 0u;
-          uint32_t nt = s_cnt[mask];
-          if (nt) {
-            cnt += nt;
-            label_insert(lh, (uint64_t)L);
-          }
-        }
+      const CellClass k = classify_cell(c);
+      for (uint32_t f = k.first; f; f &= f - 1) {
+        const uint32_t i = (uint32_t)__builtin_ctz(f);
+        cnt += s_cnt[k.row(i)];
+        label_insert(lh, (uint64_t)pick_corner(c, i));
       }
     }
     // wave reduce
@@ -454,11 +480,13 @@ __device__ __forceinline__ void stage_decode_tables(
 
 // [3] emit: recompute counts, wave prefix, write one 8-B record + the
 // 4-B label id per triangle in canonical global order.
+// 8 waves/SIMD (64 VGPRs, no scratch): the kernel waits on memory, and
+// the compiler's own choice of 67 registers gave up a wave for nothing.
 template <typename T>
-__global__ void k_emit(const T *__restrict__ labels, GridDims g,
-                       const uint32_t *__restrict__ segoff, LabelHash lh,
-                       uint32_t *__restrict__ tri_label,
-                       uint2 *__restrict__ tri_recs) {
+__global__ __launch_bounds__(256, 8) void k_emit(
+    const T *__restrict__ labels, GridDims g,
+    const uint32_t *__restrict__ segoff, LabelHash lh,
+    uint32_t *__restrict__ tri_label, uint2 *__restrict__ tri_recs) {
   // count table staged in LDS: global-memory byte gathers on the small
   // case tables were the emit kernel's dominant cost (L1 line replays)
   __shared__ uint8_t s_cnt[256];
@@ -477,38 +505,38 @@ __global__ void k_emit(const T *__restrict__ labels, GridDims g,
     const int64_t cz = row / g.ncy;
     const int64_t cx = segx * WAVE + lane;
     T c[8];
+    CellClass k;
+    k.rows = 0;
+    k.first = 0;
+    // per-label triangle counts, 4 bits at 4*i for each first corner i
+    // (MC_MAX_TRIS < 16): one round of LDS lookups serves the prefix sum
+    // and the emit walk
+    uint32_t nts = 0;
     uint32_t cnt = 0;
-    bool active = false;
     if (cx < g.ncx) {
       load_corners(labels, g.sx, sxy, cx, cy, cz, c);
-      cnt = cell_tri_count(c, s_cnt);
-      active = cnt > 0;
+      k = classify_cell(c);
+      #pragma unroll
+      for (uint32_t i = 0; i < 8; ++i) {
+        const uint32_t nt = (k.first >> i) & 1u ? s_cnt[k.row(i)] : 0u;
+        nts |= nt << (4 * i);
+        cnt += nt;
+      }
     }
     uint32_t incl = wave_incl_scan(cnt, lane);
-    uint32_t base = segoff[seg] + incl - cnt;
-    if (active) {
-      uint32_t pos = base;
-      const uint32_t cell_lin = (uint32_t)((cz * g.sy + cy) * g.sx + cx);
-      const uint32_t zero = (uint32_t)(cx == 0) | ((uint32_t)(cy == 0) << 1) |
-                            ((uint32_t)(cz == 0) << 2);
-      #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        T L = c[i];
-        if (L == 0) continue;
-        bool seen = false;
-        for (int j = 0; j < i; ++j) seen |= (c[j] == L);
-        if (seen) continue;
-        unsigned mask = 0;
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) mask |= (c[j] == L) ? (1u << j) : 0u;
-        uint32_t nt = s_cnt[mask];
-        if (!nt) continue;
-        uint32_t lid = label_lookup(lh, (uint64_t)L);
-        for (uint32_t t = 0; t < nt; ++t) {
-          tri_label[pos] = lid;
-          tri_recs[pos] = make_uint2(cell_lin, mask | (t << 8) | (zero << 11));
-          ++pos;
-        }
+    uint32_t pos = segoff[seg] + incl - cnt;
+    const uint32_t cell_lin = (uint32_t)((cz * g.sy + cy) * g.sx + cx);
+    const uint32_t zero = (uint32_t)(cx == 0) | ((uint32_t)(cy == 0) << 1) |
+                          ((uint32_t)(cz == 0) << 2);
+    for (uint32_t f = k.first; f; f &= f - 1) {
+      const uint32_t i = (uint32_t)__builtin_ctz(f);
+      const uint32_t mask = k.row(i);
+      const uint32_t nt = (nts >> (4 * i)) & 15u;
+      const uint32_t lid = label_lookup(lh, (uint64_t)pick_corner(c, i));
+      for (uint32_t t = 0; t < nt; ++t) {
+        tri_label[pos] = lid;
+        tri_recs[pos] = make_uint2(cell_lin, mask | (t << 8) | (zero << 11));
+        ++pos;
       }
     }
   }

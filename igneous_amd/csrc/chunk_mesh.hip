@@ -1,7 +1,7 @@
 // chunk_mesh.hip — grid-chunk and clip one mesh on the device (the
 // multires merge's zmesh.chunk_mesh call sites, reference multires.py:550
-// and :574). Included from meshgine.hip after the ctx helpers (mg_ctx,
-// ensure, scan_u32, sort_pairs, SET_ERR, HIP_TRY, empty_meshset).
+// and :574). Included from meshgine.hip after the ctx helpers (mg_ctx.h):
+// the kernels first, then their host driver.
 //
 // Contract: bit-equal to igneous_amd/meshops.py
 // chunk_mesh + consolidate — the same cells, the same dict order, the same
@@ -526,28 +526,28 @@ static int cm_count(mg_ctx *c, CmCall &k, const float *verts,
                     const uint32_t *faces) {
   hipStream_t s = c->stream;
   const uint64_t T = k.ntris;
-  if (ensure(c, c->cm_verts, (uint64_t)k.nverts * 12 + 12)) return 61;
-  if (ensure(c, c->cm_faces, T * 12 + 12)) return 61;
-  if (ensure(c, c->cm_ncells, (T + 1) * 4)) return 61;
-  if (ensure(c, c->cm_pair_off, (T + 1) * 4)) return 61;
-  if (ensure(c, c->cm_misc, sizeof(CmMisc))) return 61;
+  if (ensure(c, c->cm_verts, 3 * (uint64_t)k.nverts + 3)) return 61;
+  if (ensure(c, c->cm_faces, 3 * T + 3)) return 61;
+  if (ensure(c, c->cm_ncells, T + 1)) return 61;
+  if (ensure(c, c->cm_pair_off, T + 1)) return 61;
+  if (ensure(c, c->cm_misc, 1)) return 61;
   CmMisc init = {};
   for (int a = 0; a < 3; ++a) {
     init.bb_lo[a] = INT32_MAX;
     init.bb_hi[a] = INT32_MIN;
   }
-  HIP_TRY(c, hipMemcpyAsync(c->cm_misc.ptr, &init, sizeof(init),
+  HIP_TRY(c, hipMemcpyAsync(c->cm_misc.get(), &init, sizeof(init),
                             hipMemcpyHostToDevice, s), 61);
-  HIP_TRY(c, hipMemcpyAsync(c->cm_verts.ptr, verts, (uint64_t)k.nverts * 12,
-                            hipMemcpyHostToDevice, s), 61);
-  HIP_TRY(c, hipMemcpyAsync(c->cm_faces.ptr, faces, T * 12,
+  HIP_TRY(c, hipMemcpyAsync(c->cm_verts.get(), verts,
+                            (uint64_t)k.nverts * 12, hipMemcpyHostToDevice,
+                            s), 61);
+  HIP_TRY(c, hipMemcpyAsync(c->cm_faces.get(), faces, T * 12,
                             hipMemcpyHostToDevice, s), 61);
   hipLaunchKernelGGL(k_cm_face_count, dim3(cm_blocks(T + 1)), dim3(CM_BLK), 0,
-                     s, (const float *)c->cm_verts.ptr,
-                     (const uint32_t *)c->cm_faces.ptr, k.ntris, k.g,
-                     (uint32_t *)c->cm_ncells.ptr, (CmMisc *)c->cm_misc.ptr);
+                     s, c->cm_verts.get(), c->cm_faces.get(), k.ntris, k.g,
+                     c->cm_ncells.get(), c->cm_misc.get());
   CmMisc m;
-  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.ptr, sizeof(m),
+  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.get(), sizeof(m),
                             hipMemcpyDeviceToHost, s), 61);
   HIP_TRY(c, hipStreamSynchronize(s), 61);
   if (m.err & CM_ERR_CELL_RANGE) {
@@ -572,8 +572,7 @@ static int cm_count(mg_ctx *c, CmCall &k, const float *verts,
   }
   k.dn.ny = (uint32_t)n[1];
   k.dn.nz = (uint32_t)n[2];
-  return scan_u32(c, (uint32_t *)c->cm_ncells.ptr,
-                  (uint32_t *)c->cm_pair_off.ptr, T + 1, s,
+  return scan_u32(c, c->cm_ncells.get(), c->cm_pair_off.get(), T + 1, s,
                   "chunk_mesh pair scan size query failed",
                   "chunk_mesh pair scan failed", 63);
 }
@@ -585,41 +584,34 @@ static int cm_pairs(mg_ctx *c, CmCall &k,
                     rocprim::double_buffer<uint32_t> &vals) {
   hipStream_t s = c->stream;
   const uint64_t P = k.P;
-  if (ensure(c, c->cm_npts, P * 4 + 4)) return 64;
-  if (ensure(c, c->cm_npts_s, (P + 1) * 4)) return 64;
-  if (ensure(c, c->cm_fhead, (P + 1) * 4)) return 64;
-  if (ensure(c, c->cm_coff, (P + 1) * 4)) return 64;
-  if (ensure(c, c->cm_ford, (P + 1) * 4)) return 64;
+  for (auto *b : {&c->cm_npts, &c->cm_npts_s, &c->cm_fhead, &c->cm_coff,
+                  &c->cm_ford})
+    if (ensure(c, *b, P + 1)) return 64;
   hipLaunchKernelGGL(k_cm_pair, dim3(cm_blocks(P)), dim3(CM_BLK), 0, s,
-                     (const float *)c->cm_verts.ptr,
-                     (const uint32_t *)c->cm_faces.ptr,
-                     (const uint32_t *)c->cm_pair_off.ptr, k.ntris, k.P, k.g,
-                     k.dn, keys.current(), vals.current(),
-                     (uint32_t *)c->cm_npts.ptr, (CmMisc *)c->cm_misc.ptr);
+                     c->cm_verts.get(), c->cm_faces.get(),
+                     c->cm_pair_off.get(), k.ntris, k.P, k.g, k.dn,
+                     keys.current(), vals.current(), c->cm_npts.get(),
+                     c->cm_misc.get());
   if (int e = sort_pairs(c, keys, vals, P, 0, cm_bits(2 * k.ndense), s,
                          "chunk_mesh fragment sort size query failed",
                          "chunk_mesh fragment sort failed", 65))
     return e;
   hipLaunchKernelGGL(k_cm_frag_gather, dim3(cm_blocks(P + 1)), dim3(CM_BLK),
-                     0, s, keys.current(), vals.current(),
-                     (const uint32_t *)c->cm_npts.ptr, k.P,
-                     (uint32_t *)c->cm_npts_s.ptr,
-                     (uint32_t *)c->cm_fhead.ptr);
-  if (int e = scan_u32(c, (uint32_t *)c->cm_npts_s.ptr,
-                       (uint32_t *)c->cm_coff.ptr, P + 1, s,
+                     0, s, keys.current(), vals.current(), c->cm_npts.get(),
+                     k.P, c->cm_npts_s.get(), c->cm_fhead.get());
+  if (int e = scan_u32(c, c->cm_npts_s.get(), c->cm_coff.get(), P + 1, s,
                        "chunk_mesh corner scan size query failed",
                        "chunk_mesh corner scan failed", 65))
     return e;
-  if (int e = scan_u32(c, (uint32_t *)c->cm_fhead.ptr,
-                       (uint32_t *)c->cm_ford.ptr, P + 1, s,
+  if (int e = scan_u32(c, c->cm_fhead.get(), c->cm_ford.get(), P + 1, s,
                        "chunk_mesh cell scan size query failed",
                        "chunk_mesh cell scan failed", 65))
     return e;
   CmMisc m;
   uint32_t ncellp = 0;
-  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.ptr, sizeof(m),
+  HIP_TRY(c, hipMemcpyAsync(&m, c->cm_misc.get(), sizeof(m),
                             hipMemcpyDeviceToHost, s), 66);
-  HIP_TRY(c, hipMemcpyAsync(&ncellp, (uint32_t *)c->cm_ford.ptr + P, 4,
+  HIP_TRY(c, hipMemcpyAsync(&ncellp, c->cm_ford.get() + P, 4,
                             hipMemcpyDeviceToHost, s), 66);
   HIP_TRY(c, hipStreamSynchronize(s), 66);
   if (m.err & CM_ERR_POLY_OVERFLOW) {
@@ -642,24 +634,21 @@ static int cm_emit(mg_ctx *c, const CmCall &k, const uint32_t *keys_s,
                    const uint32_t *order) {
   hipStream_t s = c->stream;
   const uint64_t C = k.C, stride = (uint64_t)k.ncellp + 1;
-  if (ensure(c, c->cm_pos, C * 12 + 12)) return 68;
-  if (ensure(c, c->cm_cfrag, C * 4 + 4)) return 68;
-  if (ensure(c, c->cm_ccell, C * 4 + 4)) return 68;
-  if (ensure(c, c->cm_cells, stride * CM_CELL_FIELDS * 4)) return 68;
+  if (ensure(c, c->cm_pos, 3 * C + 3)) return 68;
+  if (ensure(c, c->cm_cfrag, C + 1)) return 68;
+  if (ensure(c, c->cm_ccell, C + 1)) return 68;
+  if (ensure(c, c->cm_cells, stride * CM_CELL_FIELDS)) return 68;
   // FIRSTP stays 0xFFFFFFFF for a cell whose fragments were all empty
-  HIP_TRY(c, hipMemsetAsync(c->cm_cells.ptr, 0xFF,
+  HIP_TRY(c, hipMemsetAsync(c->cm_cells.get(), 0xFF,
                             stride * CM_CELL_FIELDS * 4, s), 68);
   hipLaunchKernelGGL(k_cm_emit, dim3(cm_blocks(k.P)), dim3(CM_BLK), 0, s,
-                     (const float *)c->cm_verts.ptr,
-                     (const uint32_t *)c->cm_faces.ptr,
-                     (const uint32_t *)c->cm_pair_off.ptr, k.ntris, k.P, k.g,
-                     keys_s, order, (const uint32_t *)c->cm_coff.ptr,
-                     (const uint32_t *)c->cm_fhead.ptr,
-                     (const uint32_t *)c->cm_ford.ptr, k.C,
-                     (uint32_t)stride, (float *)c->cm_pos.ptr,
-                     (uint32_t *)c->cm_cfrag.ptr,
-                     (uint32_t *)c->cm_ccell.ptr,
-                     (uint32_t *)c->cm_cells.ptr);
+                     c->cm_verts.get(), c->cm_faces.get(),
+                     c->cm_pair_off.get(), k.ntris, k.P, k.g, keys_s, order,
+                     c->cm_coff.get(), c->cm_fhead.get(), c->cm_ford.get(),
+                     k.C, (uint32_t)stride, c->cm_pos.get(),
+                     c->cm_cfrag.get(), c->cm_ccell.get(),
+                     c->cm_cells.get());
+  HIP_TRY(c, hipGetLastError(), 68);
   return 0;
 }
 
@@ -667,26 +656,21 @@ static int cm_emit(mg_ctx *c, const CmCall &k, const uint32_t *keys_s,
 static int cm_weld(mg_ctx *c, const CmCall &k) {
   hipStream_t s = c->stream;
   const uint64_t C = k.C;
-  if (ensure(c, c->cm_wkey, C * 4 + 4)) return 69;
-  if (ensure(c, c->cm_wkey_alt, C * 4 + 4)) return 69;
-  if (ensure(c, c->cm_wval, C * 4 + 4)) return 69;
-  if (ensure(c, c->cm_wval_alt, C * 4 + 4)) return 69;
-  if (ensure(c, c->cm_whead, (C + 1) * 4)) return 69;
-  if (ensure(c, c->cm_wrun, (C + 1) * 4)) return 69;
-  if (ensure(c, c->cm_head_pos, C * 4 + 4)) return 69;
-  if (ensure(c, c->cm_rep, C * 4 + 4)) return 69;
-  rocprim::double_buffer<uint32_t> keys((uint32_t *)c->cm_wkey.ptr,
-                                        (uint32_t *)c->cm_wkey_alt.ptr);
-  rocprim::double_buffer<uint32_t> vals((uint32_t *)c->cm_wval.ptr,
-                                        (uint32_t *)c->cm_wval_alt.ptr);
-  const float *pos = (const float *)c->cm_pos.ptr;
-  const uint32_t *ccell = (const uint32_t *)c->cm_ccell.ptr;
+  for (auto *b : {&c->cm_wkey, &c->cm_wkey_alt, &c->cm_wval, &c->cm_wval_alt,
+                  &c->cm_whead, &c->cm_wrun, &c->cm_head_pos, &c->cm_rep})
+    if (ensure(c, *b, C + 1)) return 69;
+  rocprim::double_buffer<uint32_t> keys(c->cm_wkey.get(),
+                                        c->cm_wkey_alt.get());
+  rocprim::double_buffer<uint32_t> vals(c->cm_wval.get(),
+                                        c->cm_wval_alt.get());
+  const float *pos = c->cm_pos.get();
+  const uint32_t *ccell = c->cm_ccell.get();
   hipLaunchKernelGGL(k_iota, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
                      vals.current(), C);
   for (int which = 0; which < 4; ++which) {
     hipLaunchKernelGGL(k_cm_weld_key, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
-                       (const uint32_t *)vals.current(), pos, ccell, k.C,
-                       which, keys.current());
+                       vals.current(), pos, ccell, k.C, which,
+                       keys.current());
     unsigned bits = which == 3 ? cm_bits(k.ncellp) : 32u;
     if (int e = sort_pairs(c, keys, vals, C, 0, bits, s,
                            "chunk_mesh weld sort size query failed",
@@ -694,8 +678,8 @@ static int cm_weld(mg_ctx *c, const CmCall &k) {
       return e;
   }
   const uint32_t *sorted = vals.current();
-  uint32_t *whead = (uint32_t *)c->cm_whead.ptr;
-  uint32_t *wrun = (uint32_t *)c->cm_wrun.ptr;
+  uint32_t *whead = c->cm_whead.get();
+  uint32_t *wrun = c->cm_wrun.get();
   hipLaunchKernelGGL(k_cm_heads, dim3(cm_blocks(C + 1)), dim3(CM_BLK), 0, s,
                      sorted, pos, ccell, k.C, whead);
   if (int e = scan_u32(c, whead, wrun, C + 1, s,
@@ -703,12 +687,11 @@ static int cm_weld(mg_ctx *c, const CmCall &k) {
                        "chunk_mesh run scan failed", 70))
     return e;
   hipLaunchKernelGGL(k_cm_head_pos, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
-                     sorted, (const uint32_t *)whead, (const uint32_t *)wrun,
-                     k.C, (uint32_t *)c->cm_head_pos.ptr);
+                     sorted, whead, wrun, k.C, c->cm_head_pos.get());
   hipLaunchKernelGGL(k_cm_rep, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
-                     sorted, (const uint32_t *)whead, (const uint32_t *)wrun,
-                     (const uint32_t *)c->cm_head_pos.ptr, k.C,
-                     (uint32_t *)c->cm_rep.ptr);
+                     sorted, whead, wrun, c->cm_head_pos.get(), k.C,
+                     c->cm_rep.get());
+  HIP_TRY(c, hipGetLastError(), 70);
   return 0;
 }
 
@@ -716,21 +699,19 @@ static int cm_weld(mg_ctx *c, const CmCall &k) {
 static int cm_faces(mg_ctx *c, const CmCall &k, const uint32_t *order) {
   hipStream_t s = c->stream;
   const uint64_t C = k.C, stride = (uint64_t)k.ncellp + 1;
-  if (ensure(c, c->cm_keep, (C + 1) * 4)) return 71;
-  if (ensure(c, c->cm_used, (C + 1) * 4)) return 71;
-  if (ensure(c, c->cm_vid, (C + 1) * 4)) return 71;
-  if (ensure(c, c->cm_fslot, (C + 1) * 4)) return 71;
-  if (ensure(c, c->cm_out_v, C * 12 + 12)) return 71;
-  if (ensure(c, c->cm_out_f, C * 12 + 12)) return 71;
-  const uint32_t *cfrag = (const uint32_t *)c->cm_cfrag.ptr;
-  const uint32_t *ccell = (const uint32_t *)c->cm_ccell.ptr;
-  const uint32_t *coff = (const uint32_t *)c->cm_coff.ptr;
-  const uint32_t *rep = (const uint32_t *)c->cm_rep.ptr;
-  uint32_t *keep = (uint32_t *)c->cm_keep.ptr;
-  uint32_t *used = (uint32_t *)c->cm_used.ptr;
-  uint32_t *vid = (uint32_t *)c->cm_vid.ptr;
-  uint32_t *fslot = (uint32_t *)c->cm_fslot.ptr;
-  uint32_t *cells = (uint32_t *)c->cm_cells.ptr;
+  for (auto *b : {&c->cm_keep, &c->cm_used, &c->cm_vid, &c->cm_fslot})
+    if (ensure(c, *b, C + 1)) return 71;
+  if (ensure(c, c->cm_out_v, 3 * C + 3)) return 71;
+  if (ensure(c, c->cm_out_f, 3 * C + 3)) return 71;
+  const uint32_t *cfrag = c->cm_cfrag.get();
+  const uint32_t *ccell = c->cm_ccell.get();
+  const uint32_t *coff = c->cm_coff.get();
+  const uint32_t *rep = c->cm_rep.get();
+  uint32_t *keep = c->cm_keep.get();
+  uint32_t *used = c->cm_used.get();
+  uint32_t *vid = c->cm_vid.get();
+  uint32_t *fslot = c->cm_fslot.get();
+  uint32_t *cells = c->cm_cells.get();
   HIP_TRY(c, hipMemsetAsync(used, 0, (C + 1) * 4, s), 71);
   hipLaunchKernelGGL(k_cm_faces, dim3(cm_blocks(C + 1)), dim3(CM_BLK), 0, s,
                      cfrag, ccell, coff, order, rep, k.C, (uint32_t)stride,
@@ -745,60 +726,48 @@ static int cm_faces(mg_ctx *c, const CmCall &k, const uint32_t *order) {
     return e;
   if (C > 0)
     hipLaunchKernelGGL(k_cm_write, dim3(cm_blocks(C)), dim3(CM_BLK), 0, s,
-                     cfrag, ccell, coff, rep, (const uint32_t *)keep,
-                     (const uint32_t *)used, (const uint32_t *)vid,
-                     (const uint32_t *)fslot, (const float *)c->cm_pos.ptr,
-                     (const uint32_t *)cells, k.C, (float *)c->cm_out_v.ptr,
-                     (uint32_t *)c->cm_out_f.ptr);
+                     cfrag, ccell, coff, rep, keep, used, vid, fslot,
+                     c->cm_pos.get(), cells, k.C, c->cm_out_v.get(),
+                     c->cm_out_f.get());
   hipLaunchKernelGGL(k_cm_cell_meta, dim3(cm_blocks(stride)), dim3(CM_BLK),
-                     0, s, (const uint32_t *)vid, (const uint32_t *)fslot,
-                     k.ncellp, k.C, (uint32_t)stride, cells);
+                     0, s, vid, fslot, k.ncellp, k.C, (uint32_t)stride,
+                     cells);
+  HIP_TRY(c, hipGetLastError(), 72);
   return 0;
 }
 
-// the descriptor of a chunk_mesh result: the mg_meshset layout of
-// extract_meshset plus out_order[nmeshes] behind nf_arr
-static mg_meshset *cm_alloc_meshset(uint32_t n, uint32_t **p_order) {
-  size_t meta_off = sizeof(mg_meshset) + sizeof(mg_mesh) * n;
-  mg_meshset *ms =
-      (mg_meshset *)calloc(1, meta_off + (size_t)n * 28 + 2 * sizeof(void *));
-  if (!ms) return nullptr;
-  ms->nmeshes = n;
-  ms->meshes = (mg_mesh *)((char *)ms + sizeof(mg_meshset));
-  ms->labels_arr = (uint64_t *)((char *)ms + meta_off);
-  ms->voff_arr = (uint32_t *)(ms->labels_arr + n);
-  ms->nv_arr = ms->voff_arr + n;
-  ms->foff_arr = ms->nv_arr + n;
-  ms->nf_arr = ms->foff_arr + n;
-  *p_order = ms->nf_arr + n;
-  return ms;
+// field f of a copy of c->cm_cells: CM_CELL_FIELDS u32 arrays of `stride`
+// (= ncellp + 1) entries each, entry ncellp = the totals
+static const uint32_t *cm_cells_view(const uint32_t *cells, int f,
+                                     uint64_t stride) {
+  return cells + f * stride;
 }
 
 // [7] D2H into the ctx's pinned staging + the descriptor: one mesh per
 // non-empty cell by ascending label (= lexicographic cell order), and the
-// host function's dict order in out_order.
+// host function's dict order in out_order[nmeshes] behind nf_arr.
 static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
                       const uint32_t **out_order) {
   hipStream_t s = c->stream;
   const uint64_t stride = (uint64_t)k.ncellp + 1;
   std::vector<uint32_t> cells(stride * CM_CELL_FIELDS);
-  HIP_TRY(c, hipMemcpyAsync(cells.data(), c->cm_cells.ptr,
+  HIP_TRY(c, hipMemcpyAsync(cells.data(), c->cm_cells.get(),
                             cells.size() * 4, hipMemcpyDeviceToHost, s), 73);
   HIP_TRY(c, hipStreamSynchronize(s), 73);
-  const uint32_t *dense = &cells[CM_CELL_DENSE * stride];
-  const uint32_t *firstp = &cells[CM_CELL_FIRSTP * stride];
-  const uint32_t *vb = &cells[CM_CELL_VB * stride];
-  const uint32_t *fb = &cells[CM_CELL_FB * stride];
+  const uint32_t *dense = cm_cells_view(cells.data(), CM_CELL_DENSE, stride);
+  const uint32_t *firstp = cm_cells_view(cells.data(), CM_CELL_FIRSTP, stride);
+  const uint32_t *vb = cm_cells_view(cells.data(), CM_CELL_VB, stride);
+  const uint32_t *fb = cm_cells_view(cells.data(), CM_CELL_FB, stride);
   const uint64_t V = vb[k.ncellp], F = fb[k.ncellp];
-  if (ensure_host(c, c->h_verts, V * 12 + 12)) return 73;
-  if (ensure_host(c, c->h_faces, F * 12 + 12)) return 73;
-  float *h_verts = (float *)c->h_verts.ptr;
-  uint32_t *h_faces = (uint32_t *)c->h_faces.ptr;
+  if (ensure(c, c->h_verts, 3 * V + 3)) return 73;
+  if (ensure(c, c->h_faces, 3 * F + 3)) return 73;
+  float *h_verts = c->h_verts.get();
+  uint32_t *h_faces = c->h_faces.get();
   if (V > 0)
-    HIP_TRY(c, hipMemcpyAsync(h_verts, c->cm_out_v.ptr, V * 12,
+    HIP_TRY(c, hipMemcpyAsync(h_verts, c->cm_out_v.get(), V * 12,
                               hipMemcpyDeviceToHost, s), 73);
   if (F > 0)
-    HIP_TRY(c, hipMemcpyAsync(h_faces, c->cm_out_f.ptr, F * 12,
+    HIP_TRY(c, hipMemcpyAsync(h_faces, c->cm_out_f.get(), F * 12,
                               hipMemcpyDeviceToHost, s), 73);
   HIP_TRY(c, hipStreamSynchronize(s), 73);
 
@@ -806,12 +775,12 @@ static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
   for (uint32_t o = 0; o < k.ncellp; ++o)
     if (fb[o + 1] > fb[o]) live.push_back(o);
   const uint32_t n = (uint32_t)live.size();
-  uint32_t *order = nullptr;
-  mg_meshset *ms = cm_alloc_meshset(n, &order);
+  mg_meshset *ms = alloc_meshset(n, 1);
   if (!ms) {
     SET_ERR(c, "chunk_mesh: out of host memory");
     return 73;
   }
+  uint32_t *order = ms->nf_arr + n;
   ms->verts_base = h_verts;
   ms->faces_base = h_faces;
   ms->total_verts = V;
@@ -866,14 +835,12 @@ static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
     k.g.offset[a] = offset[a];
   }
   if (int e = cm_count(c, k, verts, faces)) return e;
-  if (ensure(c, c->cm_fkey, (uint64_t)k.P * 4 + 4)) return 64;
-  if (ensure(c, c->cm_fkey_alt, (uint64_t)k.P * 4 + 4)) return 64;
-  if (ensure(c, c->cm_fval, (uint64_t)k.P * 4 + 4)) return 64;
-  if (ensure(c, c->cm_fval_alt, (uint64_t)k.P * 4 + 4)) return 64;
-  rocprim::double_buffer<uint32_t> keys((uint32_t *)c->cm_fkey.ptr,
-                                        (uint32_t *)c->cm_fkey_alt.ptr);
-  rocprim::double_buffer<uint32_t> vals((uint32_t *)c->cm_fval.ptr,
-                                        (uint32_t *)c->cm_fval_alt.ptr);
+  for (auto *b : {&c->cm_fkey, &c->cm_fkey_alt, &c->cm_fval, &c->cm_fval_alt})
+    if (ensure(c, *b, (uint64_t)k.P + 1)) return 64;
+  rocprim::double_buffer<uint32_t> keys(c->cm_fkey.get(),
+                                        c->cm_fkey_alt.get());
+  rocprim::double_buffer<uint32_t> vals(c->cm_fval.get(),
+                                        c->cm_fval_alt.get());
   if (int e = cm_pairs(c, k, keys, vals)) return e;
   if (int e = cm_emit(c, k, keys.current(), vals.current())) return e;
   if (k.C > 0)

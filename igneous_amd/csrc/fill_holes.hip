@@ -222,24 +222,22 @@ static inline uint32_t fill_blocks(uint64_t n) {
 static int fill_run_rounds(mg_ctx *c, const FillGeom &g, const char *what,
                            uint32_t *rounds_out) {
   hipStream_t s = c->stream;
-  uint32_t *vol = (uint32_t *)c->fill_vol.ptr;
-  uint32_t *parent = (uint32_t *)c->fill_parent.ptr;
-  uint32_t *cmin = (uint32_t *)c->fill_cmin.ptr;
-  uint32_t *cmax = (uint32_t *)c->fill_cmax.ptr;
-  uint32_t *counter = (uint32_t *)c->fill_misc.ptr;
+  uint32_t *vol = c->fill_vol.get();
+  uint32_t *parent = c->fill_parent.get();
+  uint32_t *cmin = c->fill_cmin.get();
+  uint32_t *cmax = c->fill_cmax.get();
+  uint32_t *counter = c->fill_misc.get();  // word 0: voxels rewritten
   const dim3 nb(fill_blocks(g.n)), blk(FILL_BLK);
   uint32_t productive = 0;
   for (int round = 0; round < FILL_MAX_ROUNDS; ++round) {
     HIP_TRY(c, hipMemsetAsync(counter, 0, 4, s), 52);
     hipLaunchKernelGGL(k_fill_init, nb, blk, 0, s, parent, cmin, cmax, g.n);
-    hipLaunchKernelGGL(k_fill_link, nb, blk, 0, s, (const uint32_t *)vol, g,
-                       parent);
+    hipLaunchKernelGGL(k_fill_link, nb, blk, 0, s, vol, g, parent);
     hipLaunchKernelGGL(k_fill_flatten, nb, blk, 0, s, parent, g.n);
-    hipLaunchKernelGGL(k_fill_reduce, nb, blk, 0, s, (const uint32_t *)vol, g,
-                       (const uint32_t *)parent, cmin, cmax);
-    hipLaunchKernelGGL(k_fill_rewrite, nb, blk, 0, s, vol, g,
-                       (const uint32_t *)parent, (const uint32_t *)cmin,
-                       (const uint32_t *)cmax, counter);
+    hipLaunchKernelGGL(k_fill_reduce, nb, blk, 0, s, vol, g, parent, cmin,
+                       cmax);
+    hipLaunchKernelGGL(k_fill_rewrite, nb, blk, 0, s, vol, g, parent, cmin,
+                       cmax, counter);
     HIP_TRY(c, hipGetLastError(), 52);
     uint32_t rewritten = 0;
     HIP_TRY(c, hipMemcpyAsync(&rewritten, counter, 4, hipMemcpyDeviceToHost,
@@ -268,13 +266,11 @@ static int run_fill_holes(mg_ctx *c, int dtype, int sx, int sy, int sz,
             "split the task shape", (unsigned long long)nvox);
     return 50;
   }
-  if (ensure(c, c->fill_vol, nvox * 4)) return 51;
-  if (ensure(c, c->fill_parent, nvox * 4)) return 51;
-  if (ensure(c, c->fill_cmin, nvox * 4)) return 51;
-  if (ensure(c, c->fill_cmax, nvox * 4)) return 51;
-  if (ensure(c, c->holes, nvox * esize)) return 51;
-  if (ensure(c, c->fill_misc, 256)) return 51;
-  uint32_t *vol = (uint32_t *)c->fill_vol.ptr;
+  for (auto *b : {&c->fill_vol, &c->fill_parent, &c->fill_cmin, &c->fill_cmax})
+    if (ensure(c, *b, nvox)) return 51;
+  if (ensure_bytes(c, c->holes, nvox * esize)) return 51;
+  if (ensure(c, c->fill_misc, 64)) return 51;
+  uint32_t *vol = c->fill_vol.get();
   const dim3 vnb(fill_blocks(nvox)), blk(FILL_BLK);
 
   // working volume
@@ -286,14 +282,13 @@ static int run_fill_holes(mg_ctx *c, int dtype, int sx, int sy, int sz,
     if (int e = hash_volume_labels(c, dtype, nvox, " (fill_holes)", 51, &nl))
       return e;
     const LabelHash lh = label_hash_view(c);
-    if (ensure(c, c->label_values, (uint64_t)std::max(nl, 1u) * 8))
-      return 51;
+    if (ensure(c, c->label_values, std::max(nl, 1u))) return 51;
     hipLaunchKernelGGL(k_label_values,
                        dim3((uint32_t)((c->lh_slots + 255) / 256)),
-                       dim3(256), 0, s, lh,
-                       (uint64_t *)c->label_values.ptr, c->lh_slots);
+                       dim3(256), 0, s, lh, c->label_values.get(),
+                       c->lh_slots);
     hipLaunchKernelGGL(k_fill_to_ids, vnb, blk, 0, s,
-                       (const uint64_t *)c->labels.ptr, nvox, lh, vol);
+                       c->labels.as<const uint64_t>(), nvox, lh, vol);
     HIP_TRY(c, hipGetLastError(), 51);
   }
 
@@ -327,12 +322,11 @@ static int run_fill_holes(mg_ctx *c, int dtype, int sx, int sy, int sz,
 
   // ids back to values through label_values (u64 only: u32 ids ARE labels)
   const uint64_t *values =
-      dtype == MG_U64 ? (const uint64_t *)c->label_values.ptr : nullptr;
+      dtype == MG_U64 ? c->label_values.get() : nullptr;
   by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hipLaunchKernelGGL(k_fill_finish<T>, vnb, blk, 0, s, (T *)c->labels.ptr,
-                       (T *)c->holes.ptr, (const uint32_t *)vol, values,
-                       nvox);
+    hipLaunchKernelGGL(k_fill_finish<T>, vnb, blk, 0, s, c->labels.as<T>(),
+                       c->holes.as<T>(), vol, values, nvox);
   });
   HIP_TRY(c, hipGetLastError(), 54);
   return 0;

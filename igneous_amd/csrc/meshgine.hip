@@ -41,23 +41,14 @@
 // triangle partition order is by internal id but per-label content and the
 // final label-sorted meshset are invariant).
 
-#include <atomic>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <mutex>
-#include <string>
-#include <vector>
-#include <algorithm>
+#include "mg_ctx.h"  // the context, its buffers and the shared host helpers
 
-#include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <atomic>
+#include <vector>
 
 #define MC_TABLE_QUAL __device__ static const
 #include "mc_table.h"
-
-#include "../../include/meshgine.h"
 
 // ---------------------------------------------------------------------------
 // small utilities
@@ -763,254 +754,27 @@ __global__ void k_any_active(const uint8_t *active, uint32_t nlabels,
 #include "simplify.hip"
 
 // ---------------------------------------------------------------------------
-// context / host side
-
-// Move-only owner of one hipMalloc'd (DevBuf) or pinned (HostBuf) block.
-// Moving nulls the source, so std::swap(c->faces, c->simp_faces_alt)
-// exchanges the blocks without a free in the swap's temporary.
-template <hipError_t (*FREE)(void *)>
-struct OwnedBuf {
-  void *ptr = nullptr;
-  size_t cap = 0;
-  OwnedBuf() = default;
-  OwnedBuf(const OwnedBuf &) = delete;
-  OwnedBuf &operator=(const OwnedBuf &) = delete;
-  OwnedBuf(OwnedBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) {
-    o.ptr = nullptr;
-    o.cap = 0;
-  }
-  OwnedBuf &operator=(OwnedBuf &&o) noexcept {
-    if (this != &o) {
-      release();
-      ptr = o.ptr;
-      cap = o.cap;
-      o.ptr = nullptr;
-      o.cap = 0;
-    }
-    return *this;
-  }
-  ~OwnedBuf() { release(); }
-  void release() {
-    if (ptr) (void)FREE(ptr);
-    ptr = nullptr;
-    cap = 0;
-  }
-};
-using DevBuf = OwnedBuf<hipFree>;
-using HostBuf = OwnedBuf<hipHostFree>;
-
-// Every device buffer of a context (grow-only cache). This is the one
-// list: ~mg_ctx releases the struct as a whole.
-struct DeviceBuffers {
-  DevBuf labels, segcnt, segoff, scan_tmp,
-      lh_keys, lh_vals, lh_misc,
-      tri_label, tri_label_alt, order, order_alt, tri_keys, keys_sorted,
-      tri_off, sort_tmp,
-      wh_keys, vtx_scan, verts, faces, vbase,
-      label_values,
-      simp_fq, simp_valid, simp_pk, simp_pk_alt, simp_pv, simp_pv_alt,
-      simp_Q, simp_pick, simp_remap, simp_flab, simp_flab_alt,
-      simp_faces_alt, simp_verts_alt, simp_vbase_alt, simp_meta, simp_ref,
-      simp_keep, simp_keep_scan, simp_park, simp_first, simp_troff_final,
-      simp_deg, simp_adj, simp_rh, simp_accept,
-      map_tab, map_keys, map_vals,  // label map table + staged pairs
-      // fill_holes: u32 working volume, union-find parents, per-root
-      // neighbour min/max, rewrite counter, resident hole volume
-      fill_vol, fill_parent, fill_cmin, fill_cmax, fill_misc, holes,
-      // chunk_mesh (chunk_mesh.hip): inputs, per-face / per-pair /
-      // per-corner / per-cell arrays, the two sorts' double buffers, outputs
-      cm_verts, cm_faces, cm_ncells, cm_pair_off, cm_misc,
-      cm_fkey, cm_fkey_alt, cm_fval, cm_fval_alt,
-      cm_npts, cm_npts_s, cm_fhead, cm_coff, cm_ford,
-      cm_pos, cm_cfrag, cm_ccell, cm_cells,
-      cm_wkey, cm_wkey_alt, cm_wval, cm_wval_alt, cm_whead, cm_wrun,
-      cm_head_pos, cm_rep, cm_keep, cm_used, cm_vid, cm_fslot,
-      cm_out_v, cm_out_f;
-};
-
-// Timing / ordering events of one mesh_chunk_impl call. EV_H2D_END is
-// recorded TWICE: after the upload, and again at the start of the count
-// pass — so ms_h2d (EV_START..EV_H2D_END) spans upload + dust + label map
-// + fill, and ms_count starts where it ends. Benchmarks and the stored
-// profiles were taken with that meaning; keep it.
-enum {
-  EV_START = 0,
-  EV_H2D_END,
-  EV_COUNT_END,
-  EV_SCAN_END,
-  EV_EMIT_END,
-  EV_PARTITION_END,
-  EV_WELD_END,
-  EV_END,           // after the extract
-  EV_SIMPLIFY_END,
-  EV_SIMP_FORK,     // stream2 waits for the simplify setup
-  EV_SIMP_JOIN,     // stream waits for stream2's bands
-  EV_MAP_START,
-  EV_MAP_END,
-  EV_FILL_START,
-  EV_FILL_END,
-  EV_COUNT_
-};
-
-struct mg_ctx : DeviceBuffers {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // concurrent simplify band
-  std::mutex lock;
-  std::string err;
-  mg_stats stats = {};
-  // hole volume stashed by the last mg_mesh_chunk_filled (mg_mesh_holes
-  // consumes it)
-  bool holes_valid = false;
-  int holes_sx = 0, holes_sy = 0, holes_sz = 0, holes_dtype = 0;
-  uint64_t lh_slots = 1ull << 20;
-  HostBuf h_verts, h_faces;  // pinned output staging, reused across calls
-  hipEvent_t ev[EV_COUNT_] = {};
-
-  // release order: device buffers, pinned buffers, events, stream2, stream
-  ~mg_ctx() {
-    (void)hipSetDevice(device);
-    static_cast<DeviceBuffers &>(*this) = DeviceBuffers();  // frees each
-    h_verts.release();
-    h_faces.release();
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream2) (void)hipStreamDestroy(stream2);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-static thread_local std::string g_err;  // for ctx==NULL failures
-
-#define SET_ERR(ctx, ...)                                     \
-  do {                                                        \
-    char _buf[512];                                           \
-    snprintf(_buf, sizeof(_buf), __VA_ARGS__);                \
-    if (ctx) (ctx)->err = _buf; else g_err = _buf;            \
-  } while (0)
-
-#define HIP_TRY(ctx, call, retcode)                           \
-  do {                                                        \
-    hipError_t _e = (call);                                   \
-    if (_e != hipSuccess) {                                   \
-      SET_ERR(ctx, "%s failed: %s (%s:%d)", #call,            \
-              hipGetErrorString(_e), __FILE__, __LINE__);     \
-      return retcode;                                         \
-    }                                                         \
-  } while (0)
-
-static int ensure_host(mg_ctx *c, HostBuf &b, size_t bytes) {
-  if (b.cap >= bytes) return 0;
-  b.release();
-  size_t want = bytes + bytes / 4;
-  if (hipHostMalloc(&b.ptr, want) != hipSuccess) {
-    if (hipHostMalloc(&b.ptr, bytes) != hipSuccess) {
-      SET_ERR(c, "hipHostMalloc(%zu) failed", bytes);
-      return 1;
-    }
-    b.cap = bytes;
-    return 0;
-  }
-  b.cap = want;
-  return 0;
-}
-
-static int ensure(mg_ctx *c, DevBuf &b, size_t bytes) {
-  if (b.cap >= bytes) return 0;
-  b.release();
-  size_t want = bytes + bytes / 4;  // 25% headroom to damp re-allocs
-  hipError_t e = hipMalloc(&b.ptr, want);
-  if (e != hipSuccess) {
-    e = hipMalloc(&b.ptr, bytes);  // retry exact
-    if (e != hipSuccess) {
-      SET_ERR(c, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-      return 1;
-    }
-    b.cap = bytes;
-    return 0;
-  }
-  b.cap = want;
-  return 0;
-}
-
-// Call f with a zero of the volume's label type, f(uint32_t{}) or
-// f(uint64_t{}), so a templated launch is written once:
-//   by_dtype(dtype, [&](auto t) { using T = decltype(t); ...k_x<T>... });
-template <typename F>
-static auto by_dtype(int dtype, F &&f) {
-  if (dtype == MG_U64) return f(uint64_t{});
-  return f(uint32_t{});
-}
-
-// rocPRIM's two-call pattern: size query, grow the temp buffer, run.
-// call(tmp_ptr, tmp_bytes) wraps the primitive; the two texts and rc are
-// the caller's error for a failed size query / a failed run.
-template <typename F>
-static int rocprim_two_call(mg_ctx *c, DevBuf &tmp, const char *err_size,
-                            const char *err_run, int rc, F call) {
-  size_t bytes = 0;
-  if (call(nullptr, bytes) != hipSuccess) {
-    SET_ERR(c, "%s", err_size);
-    return rc;
-  }
-  if (ensure(c, tmp, bytes)) return rc;
-  if (call(tmp.ptr, bytes) != hipSuccess) {
-    SET_ERR(c, "%s", err_run);
-    return rc;
-  }
-  return 0;
-}
-
-// Exclusive plus-scan of n u32 values from `in` into `out` on stream s,
-// temp storage in c->scan_tmp. In is a template parameter only so that
-// each call site keeps the iterator type it always instantiated rocPRIM
-// with (uint32_t *, or the weld's popcount transform iterator).
-template <typename In>
-static int scan_u32(mg_ctx *c, In in, uint32_t *out, size_t n, hipStream_t s,
-                    const char *err_size, const char *err_run, int rc) {
-  return rocprim_two_call(
-      c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
-        return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n,
-                                       rocprim::plus<uint32_t>(), s);
-      });
-}
-
-// Stable radix sort of n (u32 key, V value) pairs on bits [begin, end) on
-// stream s, temp storage in c->sort_tmp; results in the buffers' current().
-template <typename V>
-static int sort_pairs(mg_ctx *c, rocprim::double_buffer<uint32_t> &keys,
-                      rocprim::double_buffer<V> &vals, size_t n,
-                      unsigned begin_bit, unsigned end_bit, hipStream_t s,
-                      const char *err_size, const char *err_run, int rc) {
-  return rocprim_two_call(
-      c, c->sort_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
-        return rocprim::radix_sort_pairs(tmp, bytes, keys, vals, n,
-                                         begin_bit, end_bit, s);
-      });
-}
-
-// ---------------------------------------------------------------------------
-// label hash, host side: lh_keys/lh_vals hold c->lh_slots slots; lh_misc
-// word 0 is the id counter, word 1 the overflow flag (words 2.. are
-// scratch scalars of later stages).
+// label hash, host side: lh_keys/lh_vals hold c->lh_slots slots; the id
+// counter and the overflow flag are the first two words of c->scalars.
 
 static LabelHash label_hash_view(mg_ctx *c) {
   LabelHash lh;
-  lh.keys = (uint64_t *)c->lh_keys.ptr;
-  lh.vals = (uint32_t *)c->lh_vals.ptr;
-  lh.counter = (uint32_t *)c->lh_misc.ptr;
-  lh.overflow = (uint32_t *)c->lh_misc.ptr + 1;
+  lh.keys = c->lh_keys.get();
+  lh.vals = c->lh_vals.get();
+  lh.counter = &c->scalars->lh_counter;
+  lh.overflow = &c->scalars->lh_overflow;
   lh.nslots = c->lh_slots;
   return lh;
 }
 
-// size the hash for c->lh_slots and clear it
+// size the hash for c->lh_slots and clear it (and the scalar block)
 static int label_hash_reset(mg_ctx *c, int rc) {
-  if (ensure(c, c->lh_keys, c->lh_slots * 8)) return rc;
-  if (ensure(c, c->lh_vals, c->lh_slots * 4)) return rc;
-  if (ensure(c, c->lh_misc, 256)) return rc;
-  HIP_TRY(c, hipMemsetAsync(c->lh_keys.ptr, 0, c->lh_slots * 8, c->stream),
+  if (ensure(c, c->lh_keys, c->lh_slots)) return rc;
+  if (ensure(c, c->lh_vals, c->lh_slots)) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->lh_keys.get(), 0, c->lh_slots * 8, c->stream),
           rc);
-  HIP_TRY(c, hipMemsetAsync(c->lh_misc.ptr, 0, 256, c->stream), rc);
+  HIP_TRY(c, hipMemsetAsync(c->scalars.get(), 0, sizeof(CtxScalars),
+                            c->stream), rc);
   return 0;
 }
 
@@ -1037,11 +801,11 @@ static int hash_volume_labels(mg_ctx *c, int dtype, uint64_t nvox,
     by_dtype(dtype, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(k_dust_build<T>, dim3(4096), dim3(256), 0, s,
-                         (const T *)c->labels.ptr, nvox, lh);
+                         c->labels.as<const T>(), nvox, lh);
     });
-    uint32_t misc[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8, hipMemcpyDeviceToHost,
-                              s), rc);
+    uint32_t misc[2] = {0, 0};  // lh_counter, lh_overflow
+    HIP_TRY(c, hipMemcpyAsync(misc, &c->scalars->lh_counter, 8,
+                              hipMemcpyDeviceToHost, s), rc);
     HIP_TRY(c, hipStreamSynchronize(s), rc);
     if (!misc[1]) {
       *p_n = misc[0];
@@ -1077,6 +841,12 @@ mg_ctx *mg_init(int device_id) {
       hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) ==
           hipSuccess;
   for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  // cleared on the ctx's own stream, ahead of its first call: a memset on
+  // the null stream would open one more hardware queue per process and
+  // change how the contexts' streams share the queues
+  ok = ok && ensure(c, c->scalars, 1) == 0 &&
+       hipMemsetAsync(c->scalars.get(), 0, sizeof(CtxScalars), c->stream) ==
+           hipSuccess;
   if (!ok) {
     delete c;  // ~mg_ctx destroys whatever was created
     return nullptr;
@@ -1104,464 +874,20 @@ void mg_meshset_free(mg_meshset *ms) {
 
 }  // extern "C"
 
-// a meshset with no meshes (the caller frees it like any other)
-static mg_meshset *empty_meshset() {
-  return (mg_meshset *)calloc(1, sizeof(mg_meshset) + 2 * sizeof(void *));
+// *out = a meshset of n meshes (the caller frees it like any other)
+static int new_meshset(mg_ctx *c, uint32_t n, mg_meshset **out) {
+  *out = alloc_meshset(n, 0);
+  if (!*out) {
+    SET_ERR(c, "mesh_chunk: out of host memory");
+    return 24;
+  }
+  return 0;
 }
 
 static double ev_ms(mg_ctx *c, int a, int b) {
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, c->ev[a], c->ev[b]) != hipSuccess) return 0.0;
   return (double)ms;
-}
-
-// ---------------------------------------------------------------------------
-// GPU quadric simplification driver (kernels in simplify.hip); mirrors
-// oracle/simplify.c round for round.
-
-#define SIMP_BLK 256
-
-static inline uint32_t simp_blocks(uint64_t n) {
-  return (uint32_t)((n + SIMP_BLK - 1) / SIMP_BLK);
-}
-
-// Environment switches of the simplifier, read once per call.
-struct SimpEnv {
-  uint32_t propose;  // MG_SIMP_PROPOSE=0 disables the proposal-acceptance
-                     // second matching wave (contract knob shared with
-                     // the oracle, which reads the same variable)
-  uint32_t subs;     // MG_SIMP_SUBS: sub-rounds per quadric recompute in
-                     // the per-label kernel (contract constant, default 6
-                     // on both sides)
-  bool prof;         // MG_SIMP_PROF: per-phase cycle counters to stderr
-  bool roundhist;    // MG_SIMP_ROUNDHIST: round-count histograms to stderr
-};
-
-static SimpEnv read_simp_env() {
-  SimpEnv env = {1u, 6u, false, false};
-  const char *e = getenv("MG_SIMP_PROPOSE");
-  if (e && e[0] == '0') env.propose = 0;
-  e = getenv("MG_SIMP_SUBS");
-  if (e && e[0]) { int v = atoi(e); env.subs = v < 1 ? 1u : (uint32_t)v; }
-  env.prof = getenv("MG_SIMP_PROF") != nullptr;
-  env.roundhist = getenv("MG_SIMP_ROUNDHIST") != nullptr;
-  return env;
-}
-
-// Per-call values of one run_simplify.
-struct SimpCall {
-  SimpEnv env;
-  uint64_t L, V;     // labels, vertices (V is fixed until the final compact)
-  float max_cost;
-  // c->simp_meta: [0,L) nt_cur | [L,2L) target | [2L,3L) nt_new |
-  //               3L..: active u8[L] | any u32 (aligned)
-  uint32_t *nt_cur, *target, *nt_new;
-  uint8_t *active;
-  uint32_t *d_any;
-  unsigned long long *d_prof;  // 6 phase counters, or null
-  uint32_t *d_rh;              // round histogram (176 u32), or null
-};
-
-static int simp_alloc(mg_ctx *c, SimpCall &k, uint64_t T) {
-  const uint64_t L = k.L, V = k.V;
-  const uint64_t meta_bytes = L * 12 + ((L + 3) & ~3ull) + 4;
-  if (ensure(c, c->simp_meta, meta_bytes)) return 40;
-  k.nt_cur = (uint32_t *)c->simp_meta.ptr;
-  k.target = k.nt_cur + L;
-  k.nt_new = k.target + L;
-  k.active = (uint8_t *)(k.nt_new + L);
-  k.d_any = (uint32_t *)((char *)c->simp_meta.ptr +
-                         L * 12 + ((L + 3) & ~3ull));
-  if (ensure(c, c->simp_flab, T * 4)) return 40;
-  if (ensure(c, c->simp_flab_alt, T * 4)) return 40;
-  if (ensure(c, c->simp_faces_alt, T * 12)) return 40;
-  if (ensure(c, c->simp_fq, T * sizeof(SimpPlane))) return 40;
-  if (ensure(c, c->simp_valid, T)) return 40;
-  if (ensure(c, c->simp_pk, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pk_alt, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pv, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_pv_alt, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_Q, V * 48)) return 40;  // 12-float rows
-  if (ensure(c, c->simp_pick, V * 8)) return 40;
-  if (ensure(c, c->simp_remap, V * 4)) return 40;
-  if (ensure(c, c->simp_keep, T * 4)) return 40;
-  if (ensure(c, c->simp_keep_scan, T * 4)) return 40;
-  if (ensure(c, c->simp_park, 3 * T * 4)) return 40;
-  if (ensure(c, c->simp_first, (L + 1) * 4)) return 40;
-  if (ensure(c, c->simp_troff_final, (L + 1) * 4)) return 40;
-  if (ensure(c, c->simp_deg, V * 4)) return 40;
-  if (ensure(c, c->simp_adj, V * 4)) return 40;
-  if (ensure(c, c->simp_accept, V * 4)) return 40;
-  return 0;
-}
-
-// MG_SIMP_PROF / MG_SIMP_ROUNDHIST printouts of the per-label launch
-static int simp_print_diagnostics(mg_ctx *c, const SimpCall &k) {
-  hipStream_t s = c->stream;
-  if (k.d_prof) {
-    unsigned long long hp[6];
-    HIP_TRY(c, hipMemcpyAsync(hp, k.d_prof, 48, hipMemcpyDeviceToHost, s),
-            40);
-    HIP_TRY(c, hipStreamSynchronize(s), 40);
-    const char *nm[6] = {"loophead", "planes+deg", "scan+fill",
-                         "sortaccum", "picks", "collapse+compact"};
-    fprintf(stderr, "[mg simp phases, summed tid0 cycles]");
-    for (int i = 0; i < 6; ++i) fprintf(stderr, " %s=%llu", nm[i], hp[i]);
-    fprintf(stderr, "\n");
-  }
-  if (k.d_rh) {
-    uint32_t h[176];
-    HIP_TRY(c, hipMemcpyAsync(h, k.d_rh, 176 * 4, hipMemcpyDeviceToHost, s),
-            40);
-    HIP_TRY(c, hipStreamSynchronize(s), 40);
-    fprintf(stderr, "[mg simp rounds] labels=%u sum_groups=%u "
-            "sum_subs=%u sum_nt0=%u max_cycles=%u (nt0=%u)\n",
-            h[130], h[128], h[129], h[131], h[132], h[133]);
-    unsigned long long lds_c, glob_c;
-    memcpy(&lds_c, &h[160], 8);
-    memcpy(&glob_c, &h[162], 8);
-    fprintf(stderr, "[mg simp mode split] lds: n=%u cyc=%llu | "
-            "global: n=%u cyc=%llu\n", h[164], lds_c, h[165], glob_c);
-    fprintf(stderr, "[mg simp log2-cycle hist]");
-    for (int i = 0; i < 26; ++i)
-      if (h[134 + i]) fprintf(stderr, " %d:%u", i, h[134 + i]);
-    fprintf(stderr, "\n[mg simp group hist]");
-    for (int i = 0; i < 64; ++i)
-      if (h[i]) fprintf(stderr, " %d:%u", i, h[i]);
-    fprintf(stderr, "\n[mg simp subs hist]");
-    for (int i = 0; i < 64; ++i)
-      if (h[64 + i]) fprintf(stderr, " %d:%u", i, h[64 + i]);
-    fprintf(stderr, "\n");
-  }
-  return 0;
-}
-
-// The per-label kernel, one workgroup per label, in three nv bands:
-//   nv <= 2048          CAPV=2048 on the main stream
-//   2048 < nv <= 4096   CAPV=4096 (64 KB LDS, 2 blocks/CU) on stream2 —
-//                       these used to fall into the global-array mode
-//                       whose hot per-vertex atomics serialize on L2 lines
-//   nv > 4096           CAPV=2048 (global-array mode) on stream2
-// stream2's bands run concurrently with the main band.
-static int simp_launch_labels(mg_ctx *c, const SimpCall &k) {
-  hipStream_t s = c->stream;
-  auto launch_band = [&](auto fn, hipStream_t st, uint32_t nv_lo,
-                         uint32_t nv_hi) {
-    hipLaunchKernelGGL(fn, dim3((uint32_t)k.L), dim3(SIMP_LABEL_BS), 0,
-                       st, (uint32_t *)c->faces.ptr,
-                       (uint32_t *)c->simp_faces_alt.ptr,
-                       (const uint32_t *)c->tri_off.ptr,
-                       (const uint32_t *)c->vbase.ptr,
-                       (float *)c->verts.ptr, (float *)c->simp_Q.ptr,
-                       (unsigned long long *)c->simp_pick.ptr,
-                       (uint32_t *)c->simp_remap.ptr,
-                       (uint32_t *)c->simp_deg.ptr,
-                       (uint32_t *)c->simp_adj.ptr,
-                       (uint32_t *)c->simp_pk.ptr,
-                       (SimpPlane *)c->simp_fq.ptr,
-                       k.nt_cur, k.target, k.active,
-                       (uint32_t *)c->simp_park.ptr, k.d_prof, k.d_rh,
-                       k.max_cost, (uint32_t)k.L, SIMP_BIG_CAP, k.env.subs,
-                       nv_lo, nv_hi,
-                       (uint32_t *)c->simp_accept.ptr, k.env.propose);
-  };
-  // record BEFORE enqueuing the main band: stream2 must wait only for the
-  // shared setup, so its bands run CONCURRENT with the main one
-  // (recording after it serialized them — 51 ms vs 38 ms overlapped)
-  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_FORK], s), 40);
-  HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SIMP_FORK], 0), 40);
-  launch_band(k_simplify_label<2048>, s, 0u, 2048u);
-  launch_band(k_simplify_label<4096>, c->stream2, 2048u, 4096u);
-  launch_band(k_simplify_label<2048>, c->stream2, 4096u, 0xFFFFFFFFu);
-  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_JOIN], c->stream2), 40);
-  HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_SIMP_JOIN], 0), 40);
-  HIP_TRY(c, hipGetLastError(), 40);
-  return simp_print_diagnostics(c, k);
-}
-
-// Park the faces of labels that are not active: flag the faces of active
-// labels, scan, scatter the others into the park store (simp_park) and
-// compact the flagged ones into the alt face/label arrays.
-//   p_T != null: read the surviving count back into *p_T and make the alt
-//                arrays current (a sync point);
-//   p_T == null: the force-park — nothing survives, nothing is swapped.
-static int park_inactive(mg_ctx *c, const SimpCall &k, uint64_t T,
-                         const char *err_size, const char *err_run, int rc,
-                         uint64_t *p_T) {
-  hipStream_t s = c->stream;
-  const dim3 nb(simp_blocks(T)), blk(SIMP_BLK);
-  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
-  uint32_t *flab = (uint32_t *)c->simp_flab.ptr;
-  uint32_t *keep = (uint32_t *)c->simp_keep.ptr;
-  uint32_t *keep_scan = (uint32_t *)c->simp_keep_scan.ptr;
-  hipLaunchKernelGGL(k_flag_active_faces, nb, blk, 0, s, flab, k.active,
-                     keep, T);
-  if (int e = scan_u32(c, keep, keep_scan, T, s, err_size, err_run, rc))
-    return e;
-  hipLaunchKernelGGL(k_first_label_idx, nb, blk, 0, s, flab,
-                     (uint32_t *)c->simp_first.ptr, T);
-  hipLaunchKernelGGL(k_park_scatter, nb, blk, 0, s, faces_g, flab,
-                     (const uint32_t *)keep, (const uint32_t *)keep_scan,
-                     (const uint32_t *)c->simp_first.ptr,
-                     (const uint32_t *)c->tri_off.ptr,
-                     (uint32_t *)c->simp_faces_alt.ptr,
-                     (uint32_t *)c->simp_flab_alt.ptr,
-                     (uint32_t *)c->simp_park.ptr, SIMP_BIG_CAP, T);
-  if (!p_T) {
-    HIP_TRY(c, hipGetLastError(), rc);
-    return 0;
-  }
-  uint32_t *d_total = (uint32_t *)c->lh_misc.ptr + 4;
-  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                     (const uint32_t *)keep_scan, (const uint32_t *)keep, T,
-                     d_total);
-  uint32_t act_total = 0;
-  HIP_TRY(c, hipMemcpyAsync(&act_total, d_total, 4, hipMemcpyDeviceToHost,
-                            s), rc);
-  HIP_TRY(c, hipStreamSynchronize(s), rc);
-  std::swap(c->faces, c->simp_faces_alt);
-  std::swap(c->simp_flab, c->simp_flab_alt);
-  *p_T = act_total;
-  return 0;
-}
-
-// One round of the global (big-label) path over the T working faces:
-// quadrics, matched-pair collapse, compaction, then parking of the labels
-// that just went inactive. *p_done is set when no label is active any
-// more or no face survives the compaction.
-//
-// One collapse pass per quadric recompute: the same group structure as
-// the per-label kernel and the oracle, but measured on 512^3/200 big
-// labels sub-rounds > 1 are ~5% SLOWER here (the T- and V-sized sub
-// passes dwarf the recompute they skip, unlike the per-label kernel), so
-// the contract pins big labels at 1 sub/group — hence k_update_active's
-// constant 1u.
-static int simp_global_round(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
-                             bool *p_done) {
-  hipStream_t s = c->stream;
-  const dim3 blk(SIMP_BLK), nbl((uint32_t)((k.L + 255) / 256));
-  const uint64_t T = *p_T, V = k.V;
-  // any label still active?
-  HIP_TRY(c, hipMemsetAsync(k.d_any, 0, 4, s), 41);
-  hipLaunchKernelGGL(k_any_active, nbl, dim3(256), 0, s, k.active,
-                     (uint32_t)k.L, k.d_any);
-  uint32_t any = 0;
-  HIP_TRY(c, hipMemcpyAsync(&any, k.d_any, 4, hipMemcpyDeviceToHost, s), 41);
-  HIP_TRY(c, hipStreamSynchronize(s), 41);
-  if (!any) {
-    *p_done = true;
-    return 0;
-  }
-
-  const dim3 nbt(simp_blocks(T)), nbv(simp_blocks(V));
-  const uint64_t NP = 3 * T;
-  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
-  float *verts = (float *)c->verts.ptr;
-  uint32_t *flab = (uint32_t *)c->simp_flab.ptr;
-  unsigned long long *pick = (unsigned long long *)c->simp_pick.ptr;
-  uint32_t *remap = (uint32_t *)c->simp_remap.ptr;
-  uint32_t *accept = (uint32_t *)c->simp_accept.ptr;
-  uint32_t *keep = (uint32_t *)c->simp_keep.ptr;
-  uint32_t *keep_scan = (uint32_t *)c->simp_keep_scan.ptr;
-  float *Q = (float *)c->simp_Q.ptr;
-
-  hipLaunchKernelGGL(k_face_planes, nbt, blk, 0, s, faces_g, verts, k.active,
-                     flab, (SimpPlane *)c->simp_fq.ptr,
-                     (uint8_t *)c->simp_valid.ptr, T);
-  hipLaunchKernelGGL(k_emit_vf_pairs, nbt, blk, 0, s, faces_g, k.active, flab,
-                     (uint32_t *)c->simp_pk.ptr, (uint32_t *)c->simp_pv.ptr,
-                     T);
-  // stable sort pairs by vertex (face order preserved within vertex)
-  {
-    rocprim::double_buffer<uint32_t> dk((uint32_t *)c->simp_pk.ptr,
-                                        (uint32_t *)c->simp_pk_alt.ptr);
-    rocprim::double_buffer<uint32_t> dv((uint32_t *)c->simp_pv.ptr,
-                                        (uint32_t *)c->simp_pv_alt.ptr);
-    if (int e = sort_pairs(c, dk, dv, NP, 0u, 32u, s,
-                           "simplify sort size query", "simplify sort", 42))
-      return e;
-    hipLaunchKernelGGL(k_accum_quadrics, dim3(simp_blocks(NP)), blk, 0, s,
-                       dk.current(), dv.current(),
-                       (const SimpPlane *)c->simp_fq.ptr,
-                       (const uint8_t *)c->simp_valid.ptr, Q, NP);
-  }
-  HIP_TRY(c, hipMemsetAsync(pick, 0xFF, V * 8, s), 43);
-  if (k.env.propose) HIP_TRY(c, hipMemsetAsync(accept, 0xFF, V * 4, s), 43);
-  hipLaunchKernelGGL(k_edge_pick, nbt, blk, 0, s, faces_g, k.active, flab,
-                     (const uint32_t *)c->vbase.ptr, verts, (const float *)Q,
-                     pick, k.max_cost, T);
-  hipLaunchKernelGGL(k_iota, nbv, blk, 0, s, remap, V);
-  hipLaunchKernelGGL(k_collapse, nbv, blk, 0, s, pick, verts, remap, Q, V);
-  if (k.env.propose) {
-    hipLaunchKernelGGL(k_propose, nbv, blk, 0, s,
-                       (const unsigned long long *)pick, accept, V);
-    hipLaunchKernelGGL(k_accept, nbv, blk, 0, s,
-                       (const unsigned long long *)pick,
-                       (const uint32_t *)accept, verts, remap, Q, V);
-  }
-  hipLaunchKernelGGL(k_remap_faces, nbt, blk, 0, s, faces_g,
-                     (const uint32_t *)remap, keep, T);
-  if (int e = scan_u32(c, keep, keep_scan, T, s, "keep scan size query",
-                       "keep scan", 44))
-    return e;
-  uint32_t *d_kept = (uint32_t *)c->lh_misc.ptr + 4;
-  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                     (const uint32_t *)keep_scan, (const uint32_t *)keep, T,
-                     d_kept);
-  uint32_t kept = 0;
-  HIP_TRY(c, hipMemcpyAsync(&kept, d_kept, 4, hipMemcpyDeviceToHost, s), 44);
-  HIP_TRY(c, hipMemsetAsync(k.nt_new, 0, k.L * 4, s), 44);
-  hipLaunchKernelGGL(k_compact_faces, nbt, blk, 0, s, faces_g, flab,
-                     (const uint32_t *)keep, (const uint32_t *)keep_scan,
-                     (uint32_t *)c->simp_faces_alt.ptr,
-                     (uint32_t *)c->simp_flab_alt.ptr, k.nt_new, T);
-  hipLaunchKernelGGL(k_update_active, nbl, dim3(256), 0, s, k.nt_new,
-                     k.nt_cur, k.target, k.active, k.d_any, (uint32_t)k.L,
-                     1u);
-  HIP_TRY(c, hipGetLastError(), 44);
-  HIP_TRY(c, hipStreamSynchronize(s), 44);
-  std::swap(c->faces, c->simp_faces_alt);
-  std::swap(c->simp_flab, c->simp_flab_alt);
-  *p_T = kept;
-  if (kept == 0) {
-    *p_done = true;
-    return 0;
-  }
-  // park faces of labels that just went inactive: working set keeps
-  // only active labels (late rounds touch only the active tail)
-  return park_inactive(c, k, kept, "park scan size query", "park scan", 47,
-                       p_T);
-}
-
-// Final face array (per-label slices gathered from the park store in
-// label-id order), then drop unreferenced vertices (stable) and
-// re-localize the faces. *p_T / *p_V = the final totals.
-static int simp_finalize(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
-                         uint64_t *p_V) {
-  hipStream_t s = c->stream;
-  const dim3 blk(SIMP_BLK);
-  const uint64_t L = k.L, V = k.V;
-  uint32_t *troff_final = (uint32_t *)c->simp_troff_final.ptr;
-  if (int e = scan_u32(c, k.nt_cur, troff_final, L, s,
-                       "final troff scan size", "final troff scan", 49))
-    return e;
-  uint32_t *d_total = (uint32_t *)c->lh_misc.ptr + 6;
-  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s,
-                     (const uint32_t *)troff_final, k.nt_cur, L, d_total);
-  HIP_TRY(c, hipMemcpyAsync(troff_final + L, d_total, 4,
-                            hipMemcpyDeviceToDevice, s), 49);
-  uint32_t final_total = 0;
-  HIP_TRY(c, hipMemcpyAsync(&final_total, d_total, 4, hipMemcpyDeviceToHost,
-                            s), 49);
-  HIP_TRY(c, hipStreamSynchronize(s), 49);
-  const uint64_t T = final_total;
-  if (T > 0)
-    hipLaunchKernelGGL(k_gather_final, dim3(simp_blocks(T)), blk, 0, s,
-                       (const uint32_t *)c->simp_park.ptr,
-                       (const uint32_t *)c->tri_off.ptr,
-                       (const uint32_t *)troff_final,
-                       (uint32_t *)c->faces.ptr,
-                       (uint32_t *)c->simp_flab.ptr, (uint32_t)L, T);
-  uint32_t *faces_g = (uint32_t *)c->faces.ptr;
-  std::swap(c->tri_off, c->simp_troff_final);
-
-  if (ensure(c, c->simp_ref, (V + 1) * 4)) return 45;
-  if (ensure(c, c->simp_verts_alt, V * 12 + 12)) return 45;
-  if (ensure(c, c->simp_vbase_alt, (L + 1) * 4)) return 45;
-  uint32_t *ref = (uint32_t *)c->simp_ref.ptr;
-  uint32_t *newid = (uint32_t *)c->vtx_scan.ptr;  // NC*4 >= V*4, free now
-  HIP_TRY(c, hipMemsetAsync(ref, 0, V * 4, s), 45);
-  if (T > 0)
-    hipLaunchKernelGGL(k_mark_ref, dim3(simp_blocks(3 * T)), blk, 0, s,
-                       faces_g, ref, 3 * T);
-  if (int e = scan_u32(c, ref, newid, V, s, "ref scan size query",
-                       "ref scan", 45))
-    return e;
-  uint32_t *d_newV = (uint32_t *)c->lh_misc.ptr + 5;
-  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, newid, ref, V,
-                     d_newV);
-  uint32_t newV = 0;
-  HIP_TRY(c, hipMemcpyAsync(&newV, d_newV, 4, hipMemcpyDeviceToHost, s), 45);
-  HIP_TRY(c, hipStreamSynchronize(s), 45);
-  hipLaunchKernelGGL(k_scatter_verts, dim3(simp_blocks(V)), blk, 0, s,
-                     (float *)c->verts.ptr, ref, newid,
-                     (float *)c->simp_verts_alt.ptr, V);
-  hipLaunchKernelGGL(k_new_vbase, dim3((uint32_t)((L + 2 + 255) / 256)),
-                     dim3(256), 0, s, (const uint32_t *)c->vbase.ptr, newid,
-                     (uint32_t *)c->simp_vbase_alt.ptr, (uint32_t)L, newV);
-  if (T > 0)
-    hipLaunchKernelGGL(k_localize_faces, dim3(simp_blocks(T)), blk, 0, s,
-                       faces_g, newid, (const uint32_t *)c->simp_flab.ptr,
-                       (const uint32_t *)c->simp_vbase_alt.ptr,
-                       (uint32_t *)c->simp_faces_alt.ptr, T);
-  HIP_TRY(c, hipGetLastError(), 46);
-  std::swap(c->faces, c->simp_faces_alt);
-  std::swap(c->verts, c->simp_verts_alt);
-  std::swap(c->vbase, c->simp_vbase_alt);
-  *p_T = T;
-  *p_V = newV;
-  return 0;
-}
-
-// Simplify every label of the welded mesh in the ctx (faces / verts /
-// vbase / tri_off, label per face in lab_sorted). Updates those buffers;
-// p_T/p_V become the post-simplification totals.
-static int run_simplify(mg_ctx *c, uint32_t nlabels,
-                        const uint32_t *lab_sorted,
-                        uint32_t reduction_factor, float max_error,
-                        uint64_t *p_T, uint64_t *p_V) {
-  hipStream_t s = c->stream;
-  uint64_t T = *p_T;
-  if (T == 0 || *p_V == 0) return 0;
-  SimpCall k = {};
-  k.env = read_simp_env();
-  k.L = nlabels;
-  k.V = *p_V;
-  k.max_cost = max_error * max_error;
-  if (int e = simp_alloc(c, k, T)) return e;
-
-  // faces -> global vertex ids, label per face
-  hipLaunchKernelGGL(k_globalize_faces, dim3(simp_blocks(T)), dim3(SIMP_BLK),
-                     0, s, (uint32_t *)c->faces.ptr, lab_sorted,
-                     (const uint32_t *)c->vbase.ptr,
-                     (uint32_t *)c->simp_flab.ptr, T);
-  hipLaunchKernelGGL(k_init_simplify, dim3((uint32_t)((k.L + 255) / 256)),
-                     dim3(256), 0, s, (const uint32_t *)c->tri_off.ptr,
-                     k.nt_cur, k.target, k.active, reduction_factor,
-                     (uint32_t)k.L);
-  HIP_TRY(c, hipGetLastError(), 40);
-
-  if (k.env.prof) {
-    k.d_prof = (unsigned long long *)c->lh_misc.ptr + 8;
-    HIP_TRY(c, hipMemsetAsync(k.d_prof, 0, 48, s), 40);
-  }
-  if (k.env.roundhist) {  // groups/subs per label
-    if (ensure(c, c->simp_rh, 176 * 4)) return 40;
-    k.d_rh = (uint32_t *)c->simp_rh.ptr;
-    HIP_TRY(c, hipMemsetAsync(k.d_rh, 0, 176 * 4, s), 40);
-  }
-  if (int e = simp_launch_labels(c, k)) return e;
-
-  // drop the per-label-kernel labels from the working set; park big
-  // never-active labels (their final faces are their originals)
-  if (int e = park_inactive(c, k, T, "prepark scan size", "prepark scan", 50,
-                            &T))
-    return e;
-
-  bool done = false;
-  for (int group = 0; group < 65536 && !done; ++group)
-    if (int e = simp_global_round(c, k, &T, &done)) return e;
-
-  // any faces still in the working set (round-cap exit): force-park them
-  if (T > 0) {
-    HIP_TRY(c, hipMemsetAsync(k.active, 0, k.L, s), 48);
-    if (int e = park_inactive(c, k, T, "force-park scan size query",
-                              "force-park scan", 48, nullptr))
-      return e;
-  }
-  if (int e = simp_finalize(c, k, &T, p_V)) return e;
-  *p_T = T;
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1601,7 +927,7 @@ static int upload_labels(mg_ctx *c, const ChunkCall &k,
                          const void *labels_host, uint32_t flags) {
   const size_t bytes = k.nvox * k.esize;
   if ((flags & MG_FLAG_SKIP_H2D) && c->labels.cap >= bytes) return 0;
-  if (ensure(c, c->labels, bytes)) return 11;
+  if (ensure_bytes(c, c->labels, bytes)) return 11;
   HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels_host, bytes,
                             hipMemcpyHostToDevice, c->stream), 11);
   return 0;
@@ -1615,17 +941,15 @@ static int run_dust(mg_ctx *c, const ChunkCall &k, uint64_t dust_threshold) {
     return e;
   if (ndl == 0) return 0;
   const LabelHash lh = label_hash_view(c);
-  if (ensure(c, c->order, (uint64_t)ndl * 4)) return 16;
-  HIP_TRY(c, hipMemsetAsync(c->order.ptr, 0, (uint64_t)ndl * 4, s), 16);
+  if (ensure(c, c->order, ndl)) return 16;  // voxel count per label id
+  HIP_TRY(c, hipMemsetAsync(c->order.get(), 0, (uint64_t)ndl * 4, s), 16);
   by_dtype(k.dtype, [&](auto t) {
     using T = decltype(t);
     const dim3 nb(4096), blk(256);
     hipLaunchKernelGGL(k_dust_count<T>, nb, blk, 0, s,
-                       (const T *)c->labels.ptr, k.nvox, lh,
-                       (uint32_t *)c->order.ptr);
-    hipLaunchKernelGGL(k_dust_zero<T>, nb, blk, 0, s, (T *)c->labels.ptr,
-                       k.nvox, lh, (const uint32_t *)c->order.ptr,
-                       dust_threshold);
+                       c->labels.as<const T>(), k.nvox, lh, c->order.get());
+    hipLaunchKernelGGL(k_dust_zero<T>, nb, blk, 0, s, c->labels.as<T>(),
+                       k.nvox, lh, c->order.get(), dust_threshold);
   });
   HIP_TRY(c, hipGetLastError(), 16);
   return 0;
@@ -1639,24 +963,23 @@ static int run_label_map(mg_ctx *c, const ChunkCall &k,
   const uint64_t n = map->n, nvox = k.nvox;
   MapTable mt;
   mt.nslots = next_pow2_u64(std::max<uint64_t>(2 * n, 64));
-  if (ensure(c, c->map_tab, mt.nslots * 16)) return 41;
-  if (ensure(c, c->lh_misc, 256)) return 41;
-  mt.slots = (ulonglong2 *)c->map_tab.ptr;
-  uint32_t *d_err = (uint32_t *)c->lh_misc.ptr + 2;
+  if (ensure(c, c->map_tab, mt.nslots)) return 41;
+  mt.slots = c->map_tab.get();
+  uint32_t *d_err = &c->scalars->map_err;
   HIP_TRY(c, hipEventRecord(c->ev[EV_MAP_START], s), 41);
-  HIP_TRY(c, hipMemsetAsync(c->map_tab.ptr, 0, mt.nslots * 16, s), 41);
+  HIP_TRY(c, hipMemsetAsync(mt.slots, 0, mt.nslots * 16, s), 41);
   HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, s), 41);
   if (n > 0) {
-    if (ensure(c, c->map_keys, n * 8)) return 41;
-    if (ensure(c, c->map_vals, n * 8)) return 41;
-    HIP_TRY(c, hipMemcpyAsync(c->map_keys.ptr, map->keys, n * 8,
+    if (ensure(c, c->map_keys, n)) return 41;
+    if (ensure(c, c->map_vals, n)) return 41;
+    HIP_TRY(c, hipMemcpyAsync(c->map_keys.get(), map->keys, n * 8,
                               hipMemcpyHostToDevice, s), 41);
-    HIP_TRY(c, hipMemcpyAsync(c->map_vals.ptr, map->vals, n * 8,
+    HIP_TRY(c, hipMemcpyAsync(c->map_vals.get(), map->vals, n * 8,
                               hipMemcpyHostToDevice, s), 41);
     const int bblk = 256;
     hipLaunchKernelGGL(k_map_build, dim3((uint32_t)((n + bblk - 1) / bblk)),
-                       dim3(bblk), 0, s, (const uint64_t *)c->map_keys.ptr,
-                       (const uint64_t *)c->map_vals.ptr, n, mt, d_err);
+                       dim3(bblk), 0, s, c->map_keys.get(),
+                       c->map_vals.get(), n, mt, d_err);
   }
   const uint64_t nvec = nvox / (16 / k.esize);
   const uint32_t miss_zero = map->miss == MG_MAP_MISS_ZERO;
@@ -1673,11 +996,11 @@ static int run_label_map(mg_ctx *c, const ChunkCall &k,
     using T = decltype(t);
     if (lds)  // LDS copy of the table: <= 4096 slots = 64 KB
       hipLaunchKernelGGL(k_label_map_lds<T>, dim3(mnb), dim3(mblk),
-                         mt.nslots * 16, s, (T *)c->labels.ptr, nvox, mt,
+                         mt.nslots * 16, s, c->labels.as<T>(), nvox, mt,
                          miss_zero);
     else
       hipLaunchKernelGGL(k_label_map<T>, dim3(mnb), dim3(mblk), 0, s,
-                         (T *)c->labels.ptr, nvox, mt, miss_zero);
+                         c->labels.as<T>(), nvox, mt, miss_zero);
   });
   HIP_TRY(c, hipGetLastError(), 41);
   HIP_TRY(c, hipEventRecord(c->ev[EV_MAP_END], s), 41);
@@ -1711,22 +1034,22 @@ static inline uint32_t seg_blocks(const GridDims &g, int blk) {
 static int count_pass(mg_ctx *c, ChunkCall &k, bool *p_overflow) {
   hipStream_t s = c->stream;
   const LabelHash lh = label_hash_view(c);
-  uint32_t *d_segcnt = (uint32_t *)c->segcnt.ptr;
-  uint32_t *d_segoff = (uint32_t *)c->segoff.ptr;
+  uint32_t *d_segcnt = c->segcnt.get();
+  uint32_t *d_segoff = c->segoff.get();
   const int64_t nseg = k.g.nseg;
   HIP_TRY(c, hipEventRecord(c->ev[EV_H2D_END], s), 30);  // see the enum
   by_dtype(k.dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_count<T>, dim3(seg_blocks(k.g, 256)), dim3(256), 0,
-                       s, (const T *)c->labels.ptr, k.g, d_segcnt, lh);
+                       s, c->labels.as<const T>(), k.g, d_segcnt, lh);
   });
   HIP_TRY(c, hipGetLastError(), 30);
   HIP_TRY(c, hipEventRecord(c->ev[EV_COUNT_END], s), 30);
 
   // check overflow + read label count
-  uint32_t misc[2] = {0, 0};
-  HIP_TRY(c, hipMemcpyAsync(misc, c->lh_misc.ptr, 8, hipMemcpyDeviceToHost, s),
-          30);
+  uint32_t misc[2] = {0, 0};  // lh_counter, lh_overflow
+  HIP_TRY(c, hipMemcpyAsync(misc, &c->scalars->lh_counter, 8,
+                            hipMemcpyDeviceToHost, s), 30);
   // scan segcnt -> segoff
   if (int e = scan_u32(c, d_segcnt, d_segoff, (size_t)nseg, s,
                        "seg scan size query failed", "seg scan failed", 30))
@@ -1748,8 +1071,8 @@ static int count_pass(mg_ctx *c, ChunkCall &k, bool *p_overflow) {
 // values, emit. Leaves k.nlabels / k.T; emits nothing when either is 0.
 static int run_count_emit(mg_ctx *c, ChunkCall &k) {
   hipStream_t s = c->stream;
-  if (ensure(c, c->segcnt, k.g.nseg * 4)) return 12;
-  if (ensure(c, c->segoff, k.g.nseg * 4)) return 12;
+  if (ensure(c, c->segcnt, k.g.nseg)) return 12;
+  if (ensure(c, c->segoff, k.g.nseg)) return 12;
   for (;;) {
     if (int e = label_hash_reset(c, 12)) return e;
     bool overflow = false;
@@ -1771,24 +1094,35 @@ static int run_count_emit(mg_ctx *c, ChunkCall &k) {
   }
   const LabelHash lh = label_hash_view(c);
   // label id -> value
-  if (ensure(c, c->label_values, (uint64_t)k.nlabels * 8)) return 17;
+  if (ensure(c, c->label_values, k.nlabels)) return 17;
   hipLaunchKernelGGL(k_label_values,
                      dim3((uint32_t)((c->lh_slots + 255) / 256)), dim3(256),
-                     0, s, lh, (uint64_t *)c->label_values.ptr, c->lh_slots);
+                     0, s, lh, c->label_values.get(), c->lh_slots);
   // [3] emit
-  if (ensure(c, c->tri_label, k.T * 4)) return 18;
-  if (ensure(c, c->tri_keys, k.T * 8)) return 18;
+  if (ensure(c, c->tri_label, k.T)) return 18;
+  if (ensure(c, c->tri_keys, k.T)) return 18;
   by_dtype(k.dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_emit<T>, dim3(seg_blocks(k.g, 256)), dim3(256), 0, s,
-                       (const T *)c->labels.ptr, k.g,
-                       (const uint32_t *)c->segoff.ptr, lh,
-                       (uint32_t *)c->tri_label.ptr,
-                       (uint2 *)c->tri_keys.ptr);
+                       c->labels.as<const T>(), k.g, c->segoff.get(), lh,
+                       c->tri_label.get(), c->tri_keys.get());
   });
   HIP_TRY(c, hipGetLastError(), 18);
   HIP_TRY(c, hipEventRecord(c->ev[EV_EMIT_END], s), 18);
   return 0;
+}
+
+struct TriSortView {
+  uint64_t *recs, *recs_alt;  // the 8-B records as the sort's u64 values
+  uint32_t *slots;            // decoded slot triples
+};
+
+// c->keys_sorted (5T u32 for T triangles): [sort alternate of tri_keys,
+// 2T words][slot triples, 3T words]
+static TriSortView tri_sort_view(mg_ctx *c, uint64_t T) {
+  return {reinterpret_cast<uint64_t *>(c->tri_keys.get()),
+          reinterpret_cast<uint64_t *>(c->keys_sorted.get()),
+          c->keys_sorted.get() + 2 * T};
 }
 
 // [4] stable partition by label id. Default (MG_SORT_RECS=0 reverts):
@@ -1800,44 +1134,58 @@ static int run_partition(mg_ctx *c, ChunkCall &k) {
   const uint64_t T = k.T;
   const char *sre = getenv("MG_SORT_RECS");
   const bool sort_recs = !(sre && sre[0] == '0');
-  if (ensure(c, c->keys_sorted, T * 20)) return 19;  // [sort-alt 8B] + [slot triples 12B]
-  if (ensure(c, c->tri_label_alt, T * 4)) return 19;
-  k.slots = (uint32_t *)c->keys_sorted.ptr + 2 * T;
+  if (ensure(c, c->keys_sorted, 5 * T)) return 19;
+  if (ensure(c, c->tri_label_alt, T)) return 19;
+  const TriSortView tv = tri_sort_view(c, T);
+  k.slots = tv.slots;
   const dim3 nb((uint32_t)((T + 255) / 256)), blk(256);
   unsigned end_bit = 1;
   while ((1u << end_bit) < k.nlabels) ++end_bit;
-  rocprim::double_buffer<uint32_t> d_keys(
-      (uint32_t *)c->tri_label.ptr, (uint32_t *)c->tri_label_alt.ptr);
+  rocprim::double_buffer<uint32_t> d_keys(c->tri_label.get(),
+                                          c->tri_label_alt.get());
   if (sort_recs) {
-    rocprim::double_buffer<uint64_t> d_vals(
-        (uint64_t *)c->tri_keys.ptr, (uint64_t *)c->keys_sorted.ptr);
+    rocprim::double_buffer<uint64_t> d_vals(tv.recs, tv.recs_alt);
     if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
                            "radix_sort size query failed",
                            "radix_sort failed", 19))
       return e;
-    k.rec_src = (const uint2 *)d_vals.current();
+    k.rec_src = reinterpret_cast<const uint2 *>(d_vals.current());
     k.order_sorted = nullptr;  // records already label-partitioned
   } else {
-    if (ensure(c, c->order, T * 4)) return 19;
-    if (ensure(c, c->order_alt, T * 4)) return 19;
-    hipLaunchKernelGGL(k_iota, nb, blk, 0, s, (uint32_t *)c->order.ptr, T);
-    rocprim::double_buffer<uint32_t> d_vals(
-        (uint32_t *)c->order.ptr, (uint32_t *)c->order_alt.ptr);
+    if (ensure(c, c->order, T)) return 19;
+    if (ensure(c, c->order_alt, T)) return 19;
+    hipLaunchKernelGGL(k_iota, nb, blk, 0, s, c->order.get(), T);
+    rocprim::double_buffer<uint32_t> d_vals(c->order.get(),
+                                            c->order_alt.get());
     if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
                            "radix_sort size query failed",
                            "radix_sort failed", 19))
       return e;
-    k.rec_src = (const uint2 *)c->tri_keys.ptr;
+    k.rec_src = c->tri_keys.get();
     k.order_sorted = d_vals.current();
   }
   k.lab_sorted = d_keys.current();
   // label ranges
-  if (ensure(c, c->tri_off, ((uint64_t)k.nlabels + 1) * 4)) return 19;
+  if (ensure(c, c->tri_off, (uint64_t)k.nlabels + 1)) return 19;
   hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.lab_sorted,
-                     (uint32_t *)c->tri_off.ptr, T, k.nlabels);
+                     c->tri_off.get(), T, k.nlabels);
   HIP_TRY(c, hipGetLastError(), 19);
   HIP_TRY(c, hipEventRecord(c->ev[EV_PARTITION_END], s), 19);
   return 0;
+}
+
+struct WeldScanView {
+  unsigned long long *bits;  // first-occurrence flags, one bit per corner
+  uint32_t *wscan;           // exclusive scan of the words' popcounts
+};
+
+// c->vtx_scan (NC u32 for NC corners) for the weld: [bits, nwords u64]
+// [wscan, nwords u32], nwords = ceil(NC / 64), so 3 * nwords <= NC words.
+// The simplifier, which runs after the weld is done with it, takes the
+// whole buffer as its u32 vertex renumbering (simp_finalize).
+static WeldScanView weld_scan_view(mg_ctx *c, uint64_t nwords) {
+  return {reinterpret_cast<unsigned long long *>(c->vtx_scan.get()),
+          c->vtx_scan.get() + 2 * nwords};
 }
 
 // [5] weld — direct-addressed (edge, side) table, collision-free
@@ -1851,16 +1199,15 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
             "1023x1023x511, igneous_cli/cli.py:1049-1052)", k.sx, k.sy, k.sz);
     return 20;
   }
-  if (ensure(c, c->wh_keys, wslots * 4)) return 20;   // wminp
-  if (ensure(c, c->vtx_scan, NC * 4)) return 20;
+  if (ensure(c, c->wh_keys, wslots)) return 20;   // wminp
+  if (ensure(c, c->vtx_scan, NC)) return 20;
   // not cleared: k_weld_first stores every slot that is read afterwards
-  uint32_t *wminp = (uint32_t *)c->wh_keys.ptr;
+  uint32_t *wminp = c->wh_keys.get();
   const dim3 nbt((uint32_t)((T + 255) / 256)), blk(256);
   // first positions + first-occurrence flags as a bit array, then a
-  // word-granular scan (the vtx_scan buffer is NC*4 bytes >= nwords*12)
+  // word-granular scan
   const uint64_t nwords = (NC + 63) / 64;
-  unsigned long long *bits = (unsigned long long *)c->vtx_scan.ptr;
-  uint32_t *wscan = (uint32_t *)c->vtx_scan.ptr + 2 * nwords;
+  auto [bits, wscan] = weld_scan_view(c, nwords);
   hipLaunchKernelGGL(k_weld_first,
                      dim3((uint32_t)((T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK)),
                      dim3(WELD_FIRST_BLK), 0, s, k.rec_src, k.order_sorted,
@@ -1869,7 +1216,7 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
                        wscan, nwords, s, "weld scan size query failed",
                        "weld scan failed", 20))
     return e;
-  uint32_t *d_tv = (uint32_t *)c->lh_misc.ptr + 3;
+  uint32_t *d_tv = &c->scalars->weld_verts;
   hipLaunchKernelGGL(k_total_verts, dim3(1), dim3(1), 0, s, wscan, bits,
                      nwords, d_tv);
   uint32_t tv = 0;
@@ -1878,21 +1225,16 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
   k.V = tv;
   c->stats.total_verts = tv;
 
-  if (ensure(c, c->verts, k.V * 12)) return 22;
-  if (ensure(c, c->faces, NC * 4)) return 22;
-  if (ensure(c, c->vbase, ((uint64_t)k.nlabels + 1) * 4)) return 22;
+  if (ensure(c, c->verts, 3 * k.V)) return 22;
+  if (ensure(c, c->faces, NC)) return 22;
+  if (ensure(c, c->vbase, (uint64_t)k.nlabels + 1)) return 22;
   // vbase depends only on the scan, so it goes first
   hipLaunchKernelGGL(k_vbase, dim3((k.nlabels + 1 + 255) / 256), dim3(256),
-                     0, s, (const uint32_t *)c->tri_off.ptr,
-                     (const uint32_t *)wscan,
-                     (const unsigned long long *)bits,
-                     (uint32_t *)c->vbase.ptr, k.nlabels, k.V);
-  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s,
-                     (const uint32_t *)k.slots, (const uint32_t *)wminp,
-                     k.lab_sorted, (const uint32_t *)wscan,
-                     (const unsigned long long *)bits,
-                     (const uint32_t *)c->vbase.ptr, (float *)c->verts.ptr,
-                     (uint32_t *)c->faces.ptr, (uint32_t)k.g.sx,
+                     0, s, c->tri_off.get(), wscan, bits, c->vbase.get(),
+                     k.nlabels, k.V);
+  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s, k.slots, wminp,
+                     k.lab_sorted, wscan, bits, c->vbase.get(),
+                     c->verts.get(), c->faces.get(), (uint32_t)k.g.sx,
                      (uint32_t)(k.g.sx * k.g.sy), k.rx, k.ry, k.rz,
                      k.voxel_centered ? 0.0f : 0.5f, T);
   HIP_TRY(c, hipGetLastError(), 22);
@@ -1908,44 +1250,36 @@ static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
   hipStream_t s = c->stream;
   if (flags & MG_FLAG_DEVICE_ONLY) {
     HIP_TRY(c, hipStreamSynchronize(s), 23);
-    *out = empty_meshset();
-    return 0;
+    return new_meshset(c, 0, out);
   }
   const uint32_t nlabels = k.nlabels;
   const uint64_t V = k.V, NC = 3 * k.T;
-  if (ensure_host(c, c->h_verts, V * 12 + 12)) return 24;
-  if (ensure_host(c, c->h_faces, NC * 4 + 4)) return 24;
-  float *h_verts = (float *)c->h_verts.ptr;
-  uint32_t *h_faces = (uint32_t *)c->h_faces.ptr;
+  if (ensure(c, c->h_verts, 3 * V + 3)) return 24;
+  if (ensure(c, c->h_faces, NC + 1)) return 24;
+  float *h_verts = c->h_verts.get();
+  uint32_t *h_faces = c->h_faces.get();
   std::vector<uint32_t> h_tri_off(nlabels + 1), h_vbase(nlabels + 1);
   std::vector<uint64_t> h_label_values(nlabels);
   if (V > 0)
-    HIP_TRY(c, hipMemcpyAsync(h_verts, c->verts.ptr, V * 12,
+    HIP_TRY(c, hipMemcpyAsync(h_verts, c->verts.get(), V * 12,
                               hipMemcpyDeviceToHost, s), 24);
   if (NC > 0)
-    HIP_TRY(c, hipMemcpyAsync(h_faces, c->faces.ptr, NC * 4,
+    HIP_TRY(c, hipMemcpyAsync(h_faces, c->faces.get(), NC * 4,
                               hipMemcpyDeviceToHost, s), 24);
-  HIP_TRY(c, hipMemcpyAsync(h_tri_off.data(), c->tri_off.ptr,
+  HIP_TRY(c, hipMemcpyAsync(h_tri_off.data(), c->tri_off.get(),
                             (nlabels + 1) * 4, hipMemcpyDeviceToHost, s), 24);
-  HIP_TRY(c, hipMemcpyAsync(h_vbase.data(), c->vbase.ptr, (nlabels + 1) * 4,
+  HIP_TRY(c, hipMemcpyAsync(h_vbase.data(), c->vbase.get(), (nlabels + 1) * 4,
                             hipMemcpyDeviceToHost, s), 24);
-  HIP_TRY(c, hipMemcpyAsync(h_label_values.data(), c->label_values.ptr,
+  HIP_TRY(c, hipMemcpyAsync(h_label_values.data(), c->label_values.get(),
                             nlabels * 8, hipMemcpyDeviceToHost, s), 24);
   HIP_TRY(c, hipStreamSynchronize(s), 24);
 
-  size_t meta_off = sizeof(mg_meshset) + sizeof(mg_mesh) * nlabels;
-  mg_meshset *ms = (mg_meshset *)calloc(1, meta_off + (size_t)nlabels * 24);
-  ms->nmeshes = nlabels;
-  ms->meshes = (mg_mesh *)((char *)ms + sizeof(mg_meshset));
+  mg_meshset *ms = nullptr;
+  if (int e = new_meshset(c, nlabels, &ms)) return e;
   ms->verts_base = h_verts;
   ms->faces_base = h_faces;
   ms->total_verts = V;
   ms->total_tris = k.T;
-  ms->labels_arr = (uint64_t *)((char *)ms + meta_off);
-  ms->voff_arr = (uint32_t *)(ms->labels_arr + nlabels);
-  ms->nv_arr = ms->voff_arr + nlabels;
-  ms->foff_arr = ms->nv_arr + nlabels;
-  ms->nf_arr = ms->foff_arr + nlabels;
   // order meshes by ascending label value
   std::vector<uint32_t> idx(nlabels);
   for (uint32_t i = 0; i < nlabels; ++i) idx[i] = i;
@@ -1997,7 +1331,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
 
   // trivial empty-cell-grid case
   if (g.nseg == 0) {
-    *out = empty_meshset();
+    if (int e = new_meshset(c, 0, out)) return e;
     if (fill_level) set_hole_stash(c, k);  // nothing to mesh there either
     return 0;
   }
@@ -2022,7 +1356,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
 
   if (int e = run_count_emit(c, k)) return e;
   if (k.T == 0 || k.nlabels == 0) {
-    *out = empty_meshset();
+    if (int e = new_meshset(c, 0, out)) return e;
     HIP_TRY(c, hipStreamSynchronize(s), 14);
     c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
     if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
@@ -2205,7 +1539,7 @@ int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   const size_t bytes = (size_t)sx * sy * sz * (dtype == MG_U64 ? 8 : 4);
   c->holes_valid = false;  // c->holes is overwritten
-  if (ensure(c, c->labels, bytes)) return 11;
+  if (ensure_bytes(c, c->labels, bytes)) return 11;
   HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels, bytes,
                             hipMemcpyHostToDevice, c->stream), 11);
   uint32_t rounds = 0;
@@ -2245,47 +1579,46 @@ int mg_simplify_mesh(mg_ctx *c,
   uint64_t T = ntris, V = nverts;
 
   if (reduction_factor > 1 && T > 0 && V > 0) {
-    if (ensure(c, c->verts, V * 12 + 12)) return 10;
-    if (ensure(c, c->faces, 3 * T * 4 + 4)) return 10;
-    if (ensure(c, c->tri_off, 8)) return 10;
-    if (ensure(c, c->vbase, 8)) return 10;
-    if (ensure(c, c->tri_label, T * 4 + 4)) return 10;
-    if (ensure(c, c->vtx_scan, (std::max<uint64_t>(V + 1, 3 * T)) * 4))
-      return 10;
-    HIP_TRY(c, hipMemcpyAsync(c->verts.ptr, verts, V * 12,
+    if (ensure(c, c->verts, 3 * V + 3)) return 10;
+    if (ensure(c, c->faces, 3 * T + 1)) return 10;
+    if (ensure(c, c->tri_off, 2)) return 10;
+    if (ensure(c, c->vbase, 2)) return 10;
+    if (ensure(c, c->tri_label, T + 1)) return 10;
+    // simp_finalize's vertex renumbering (weld_scan_view)
+    if (ensure(c, c->vtx_scan, std::max<uint64_t>(V + 1, 3 * T))) return 10;
+    HIP_TRY(c, hipMemcpyAsync(c->verts.get(), verts, V * 12,
                               hipMemcpyHostToDevice, s), 11);
-    HIP_TRY(c, hipMemcpyAsync(c->faces.ptr, faces, 3 * T * 4,
+    HIP_TRY(c, hipMemcpyAsync(c->faces.get(), faces, 3 * T * 4,
                               hipMemcpyHostToDevice, s), 11);
     uint32_t off_h[2] = {0, (uint32_t)T};
     uint32_t vb_h[2] = {0, (uint32_t)V};
-    HIP_TRY(c, hipMemcpyAsync(c->tri_off.ptr, off_h, 8,
+    HIP_TRY(c, hipMemcpyAsync(c->tri_off.get(), off_h, 8,
                               hipMemcpyHostToDevice, s), 11);
-    HIP_TRY(c, hipMemcpyAsync(c->vbase.ptr, vb_h, 8,
+    HIP_TRY(c, hipMemcpyAsync(c->vbase.get(), vb_h, 8,
                               hipMemcpyHostToDevice, s), 11);
-    HIP_TRY(c, hipMemsetAsync(c->tri_label.ptr, 0, T * 4, s), 11);
-    if (ensure(c, c->lh_misc, 256)) return 11;
-    int rc = run_simplify(c, 1, (const uint32_t *)c->tri_label.ptr,
-                          reduction_factor, max_error, &T, &V);
+    HIP_TRY(c, hipMemsetAsync(c->tri_label.get(), 0, T * 4, s), 11);
+    int rc = run_simplify(c, 1, c->tri_label.get(), reduction_factor,
+                          max_error, &T, &V);
     if (rc) return rc;
-    if (ensure_host(c, c->h_verts, V * 12 + 12)) return 12;
-    if (ensure_host(c, c->h_faces, 3 * T * 4 + 4)) return 12;
+    if (ensure(c, c->h_verts, 3 * V + 3)) return 12;
+    if (ensure(c, c->h_faces, 3 * T + 1)) return 12;
     if (V > 0)
-      HIP_TRY(c, hipMemcpyAsync(c->h_verts.ptr, c->verts.ptr, V * 12,
+      HIP_TRY(c, hipMemcpyAsync(c->h_verts.get(), c->verts.get(), V * 12,
                                 hipMemcpyDeviceToHost, s), 12);
     if (T > 0)
-      HIP_TRY(c, hipMemcpyAsync(c->h_faces.ptr, c->faces.ptr, 3 * T * 4,
+      HIP_TRY(c, hipMemcpyAsync(c->h_faces.get(), c->faces.get(), 3 * T * 4,
                                 hipMemcpyDeviceToHost, s), 12);
     HIP_TRY(c, hipStreamSynchronize(s), 12);
   } else {
     // no-op request: hand back a staged copy (uniform ownership)
-    if (ensure_host(c, c->h_verts, V * 12 + 12)) return 12;
-    if (ensure_host(c, c->h_faces, 3 * T * 4 + 4)) return 12;
-    memcpy(c->h_verts.ptr, verts, V * 12);
-    memcpy(c->h_faces.ptr, faces, 3 * T * 4);
+    if (ensure(c, c->h_verts, 3 * V + 3)) return 12;
+    if (ensure(c, c->h_faces, 3 * T + 1)) return 12;
+    memcpy(c->h_verts.get(), verts, V * 12);
+    memcpy(c->h_faces.get(), faces, 3 * T * 4);
   }
-  *out_verts = (const float *)c->h_verts.ptr;
+  *out_verts = c->h_verts.get();
   *out_nverts = (uint32_t)V;
-  *out_faces = (const uint32_t *)c->h_faces.ptr;
+  *out_faces = c->h_faces.get();
   *out_ntris = (uint32_t)T;
   return 0;
 }
@@ -2312,11 +1645,10 @@ int mg_chunk_mesh(mg_ctx *c,
     return 2;
   }
   if (ntris == 0) {
-    uint32_t *order = nullptr;
-    mg_meshset *ms = cm_alloc_meshset(0, &order);
+    mg_meshset *ms = alloc_meshset(0, 1);
     if (!ms) { SET_ERR(c, "chunk_mesh: out of host memory"); return 73; }
     *out = ms;
-    *out_order = order;
+    *out_order = ms->nf_arr + ms->nmeshes;
     return 0;
   }
   HIP_TRY(c, hipSetDevice(c->device), 4);

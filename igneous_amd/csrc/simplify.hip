@@ -16,7 +16,9 @@
 // vertex space is label-disjoint (vbase slices), so per-label rounds are
 // independent; a finished label freezes while others continue.
 //
-// Included by meshgine.hip (single TU).
+// Included by meshgine.hip (single TU) after mg_ctx.h and the shared small
+// kernels (k_iota, k_last_sum, k_any_active): the kernels first, then their
+// host driver (SimpEnv .. run_simplify).
 
 struct SimpPlane {
   float nx, ny, nz, d;
@@ -1029,4 +1031,426 @@ __attribute__((amdgpu_waves_per_eu(4))) void k_simplify_label(
       atomicAdd(&roundhist[131], nt0);
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// host driver of the kernels above; mirrors oracle/simplify.c round for
+// round.
+
+#define SIMP_BLK 256
+
+static inline uint32_t simp_blocks(uint64_t n) {
+  return (uint32_t)((n + SIMP_BLK - 1) / SIMP_BLK);
+}
+
+// Environment switches of the simplifier, read once per call.
+struct SimpEnv {
+  uint32_t propose;  // MG_SIMP_PROPOSE=0 disables the proposal-acceptance
+                     // second matching wave (contract knob shared with
+                     // the oracle, which reads the same variable)
+  uint32_t subs;     // MG_SIMP_SUBS: sub-rounds per quadric recompute in
+                     // the per-label kernel (contract constant, default 6
+                     // on both sides)
+  bool prof;         // MG_SIMP_PROF: per-phase cycle counters to stderr
+  bool roundhist;    // MG_SIMP_ROUNDHIST: round-count histograms to stderr
+};
+
+static SimpEnv read_simp_env() {
+  SimpEnv env = {1u, 6u, false, false};
+  const char *e = getenv("MG_SIMP_PROPOSE");
+  if (e && e[0] == '0') env.propose = 0;
+  e = getenv("MG_SIMP_SUBS");
+  if (e && e[0]) { int v = atoi(e); env.subs = v < 1 ? 1u : (uint32_t)v; }
+  env.prof = getenv("MG_SIMP_PROF") != nullptr;
+  env.roundhist = getenv("MG_SIMP_ROUNDHIST") != nullptr;
+  return env;
+}
+
+// Per-call values of one run_simplify.
+struct SimpCall {
+  SimpEnv env;
+  uint64_t L, V;     // labels, vertices (V is fixed until the final compact)
+  float max_cost;
+  // c->simp_meta: [0,L) nt_cur | [L,2L) target | [2L,3L) nt_new |
+  //               3L..: active u8[L] | any u32 (aligned)
+  uint32_t *nt_cur, *target, *nt_new;
+  uint8_t *active;
+  uint32_t *d_any;
+  unsigned long long *d_prof;  // 6 phase counters, or null
+  uint32_t *d_rh;              // round histogram (176 u32), or null
+};
+
+static int simp_alloc(mg_ctx *c, SimpCall &k, uint64_t T) {
+  const uint64_t L = k.L, V = k.V;
+  const uint64_t active_words = (L + 3) / 4;  // u8[L], padded to a word
+  if (ensure(c, c->simp_meta, 3 * L + active_words + 1)) return 40;
+  k.nt_cur = c->simp_meta.get();
+  k.target = k.nt_cur + L;
+  k.nt_new = k.target + L;
+  k.active = reinterpret_cast<uint8_t *>(k.nt_new + L);
+  k.d_any = k.nt_new + L + active_words;
+  if (ensure(c, c->simp_flab, T)) return 40;
+  if (ensure(c, c->simp_flab_alt, T)) return 40;
+  if (ensure(c, c->simp_faces_alt, 3 * T)) return 40;
+  if (ensure(c, c->simp_fq, T)) return 40;
+  if (ensure(c, c->simp_valid, T)) return 40;
+  if (ensure(c, c->simp_pk, 3 * T)) return 40;
+  if (ensure(c, c->simp_pk_alt, 3 * T)) return 40;
+  if (ensure(c, c->simp_pv, 3 * T)) return 40;
+  if (ensure(c, c->simp_pv_alt, 3 * T)) return 40;
+  if (ensure(c, c->simp_Q, 12 * V)) return 40;  // 12-float rows
+  if (ensure(c, c->simp_pick, V)) return 40;
+  if (ensure(c, c->simp_remap, V)) return 40;
+  if (ensure(c, c->simp_keep, T)) return 40;
+  if (ensure(c, c->simp_keep_scan, T)) return 40;
+  if (ensure(c, c->simp_park, 3 * T)) return 40;
+  if (ensure(c, c->simp_first, L + 1)) return 40;
+  if (ensure(c, c->simp_troff_final, L + 1)) return 40;
+  if (ensure(c, c->simp_deg, V)) return 40;
+  if (ensure(c, c->simp_adj, V)) return 40;
+  if (ensure(c, c->simp_accept, V)) return 40;
+  return 0;
+}
+
+// MG_SIMP_PROF / MG_SIMP_ROUNDHIST printouts of the per-label launch
+static int simp_print_diagnostics(mg_ctx *c, const SimpCall &k) {
+  hipStream_t s = c->stream;
+  if (k.d_prof) {
+    unsigned long long hp[6];
+    HIP_TRY(c, hipMemcpyAsync(hp, k.d_prof, 48, hipMemcpyDeviceToHost, s),
+            40);
+    HIP_TRY(c, hipStreamSynchronize(s), 40);
+    const char *nm[6] = {"loophead", "planes+deg", "scan+fill",
+                         "sortaccum", "picks", "collapse+compact"};
+    fprintf(stderr, "[mg simp phases, summed tid0 cycles]");
+    for (int i = 0; i < 6; ++i) fprintf(stderr, " %s=%llu", nm[i], hp[i]);
+    fprintf(stderr, "\n");
+  }
+  if (k.d_rh) {
+    uint32_t h[176];
+    HIP_TRY(c, hipMemcpyAsync(h, k.d_rh, 176 * 4, hipMemcpyDeviceToHost, s),
+            40);
+    HIP_TRY(c, hipStreamSynchronize(s), 40);
+    fprintf(stderr, "[mg simp rounds] labels=%u sum_groups=%u "
+            "sum_subs=%u sum_nt0=%u max_cycles=%u (nt0=%u)\n",
+            h[130], h[128], h[129], h[131], h[132], h[133]);
+    unsigned long long lds_c, glob_c;
+    memcpy(&lds_c, &h[160], 8);
+    memcpy(&glob_c, &h[162], 8);
+    fprintf(stderr, "[mg simp mode split] lds: n=%u cyc=%llu | "
+            "global: n=%u cyc=%llu\n", h[164], lds_c, h[165], glob_c);
+    fprintf(stderr, "[mg simp log2-cycle hist]");
+    for (int i = 0; i < 26; ++i)
+      if (h[134 + i]) fprintf(stderr, " %d:%u", i, h[134 + i]);
+    fprintf(stderr, "\n[mg simp group hist]");
+    for (int i = 0; i < 64; ++i)
+      if (h[i]) fprintf(stderr, " %d:%u", i, h[i]);
+    fprintf(stderr, "\n[mg simp subs hist]");
+    for (int i = 0; i < 64; ++i)
+      if (h[64 + i]) fprintf(stderr, " %d:%u", i, h[64 + i]);
+    fprintf(stderr, "\n");
+  }
+  return 0;
+}
+
+// The per-label kernel, one workgroup per label, in three nv bands:
+//   nv <= 2048          CAPV=2048 on the main stream
+//   2048 < nv <= 4096   CAPV=4096 (64 KB LDS, 2 blocks/CU) on stream2 —
+//                       these used to fall into the global-array mode
+//                       whose hot per-vertex atomics serialize on L2 lines
+//   nv > 4096           CAPV=2048 (global-array mode) on stream2
+// stream2's bands run concurrently with the main band.
+static int simp_launch_labels(mg_ctx *c, const SimpCall &k) {
+  hipStream_t s = c->stream;
+  auto launch_band = [&](auto fn, hipStream_t st, uint32_t nv_lo,
+                         uint32_t nv_hi) {
+    hipLaunchKernelGGL(fn, dim3((uint32_t)k.L), dim3(SIMP_LABEL_BS), 0,
+                       st, c->faces.get(), c->simp_faces_alt.get(),
+                       c->tri_off.get(), c->vbase.get(), c->verts.get(),
+                       c->simp_Q.get(), c->simp_pick.get(),
+                       c->simp_remap.get(), c->simp_deg.get(),
+                       c->simp_adj.get(), c->simp_pk.get(),
+                       c->simp_fq.get(), k.nt_cur, k.target, k.active,
+                       c->simp_park.get(), k.d_prof, k.d_rh,
+                       k.max_cost, (uint32_t)k.L, SIMP_BIG_CAP, k.env.subs,
+                       nv_lo, nv_hi, c->simp_accept.get(), k.env.propose);
+  };
+  // record BEFORE enqueuing the main band: stream2 must wait only for the
+  // shared setup, so its bands run CONCURRENT with the main one
+  // (recording after it serialized them — 51 ms vs 38 ms overlapped)
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_FORK], s), 40);
+  HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SIMP_FORK], 0), 40);
+  launch_band(k_simplify_label<2048>, s, 0u, 2048u);
+  launch_band(k_simplify_label<4096>, c->stream2, 2048u, 4096u);
+  launch_band(k_simplify_label<2048>, c->stream2, 4096u, 0xFFFFFFFFu);
+  HIP_TRY(c, hipEventRecord(c->ev[EV_SIMP_JOIN], c->stream2), 40);
+  HIP_TRY(c, hipStreamWaitEvent(s, c->ev[EV_SIMP_JOIN], 0), 40);
+  HIP_TRY(c, hipGetLastError(), 40);
+  return simp_print_diagnostics(c, k);
+}
+
+// Park the faces of labels that are not active: flag the faces of active
+// labels, scan, scatter the others into the park store (simp_park) and
+// compact the flagged ones into the alt face/label arrays.
+//   p_T != null: read the surviving count back into *p_T and make the alt
+//                arrays current (a sync point);
+//   p_T == null: the force-park — nothing survives, nothing is swapped.
+static int park_inactive(mg_ctx *c, const SimpCall &k, uint64_t T,
+                         const char *err_size, const char *err_run, int rc,
+                         uint64_t *p_T) {
+  hipStream_t s = c->stream;
+  const dim3 nb(simp_blocks(T)), blk(SIMP_BLK);
+  uint32_t *faces_g = c->faces.get();
+  uint32_t *flab = c->simp_flab.get();
+  uint32_t *keep = c->simp_keep.get();
+  uint32_t *keep_scan = c->simp_keep_scan.get();
+  hipLaunchKernelGGL(k_flag_active_faces, nb, blk, 0, s, flab, k.active,
+                     keep, T);
+  if (int e = scan_u32(c, keep, keep_scan, T, s, err_size, err_run, rc))
+    return e;
+  hipLaunchKernelGGL(k_first_label_idx, nb, blk, 0, s, flab,
+                     c->simp_first.get(), T);
+  hipLaunchKernelGGL(k_park_scatter, nb, blk, 0, s, faces_g, flab, keep,
+                     keep_scan, c->simp_first.get(), c->tri_off.get(),
+                     c->simp_faces_alt.get(), c->simp_flab_alt.get(),
+                     c->simp_park.get(), SIMP_BIG_CAP, T);
+  if (!p_T) {
+    HIP_TRY(c, hipGetLastError(), rc);
+    return 0;
+  }
+  uint32_t *d_total = &c->scalars->simp_kept;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, keep_scan, keep, T,
+                     d_total);
+  uint32_t act_total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&act_total, d_total, 4, hipMemcpyDeviceToHost,
+                            s), rc);
+  HIP_TRY(c, hipStreamSynchronize(s), rc);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->simp_flab, c->simp_flab_alt);
+  *p_T = act_total;
+  return 0;
+}
+
+// One round of the global (big-label) path over the T working faces:
+// quadrics, matched-pair collapse, compaction, then parking of the labels
+// that just went inactive. *p_done is set when no label is active any
+// more or no face survives the compaction.
+//
+// One collapse pass per quadric recompute: the same group structure as
+// the per-label kernel and the oracle, but measured on 512^3/200 big
+// labels sub-rounds > 1 are ~5% SLOWER here (the T- and V-sized sub
+// passes dwarf the recompute they skip, unlike the per-label kernel), so
+// the contract pins big labels at 1 sub/group — hence k_update_active's
+// constant 1u.
+static int simp_global_round(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
+                             bool *p_done) {
+  hipStream_t s = c->stream;
+  const dim3 blk(SIMP_BLK), nbl((uint32_t)((k.L + 255) / 256));
+  const uint64_t T = *p_T, V = k.V;
+  // any label still active?
+  HIP_TRY(c, hipMemsetAsync(k.d_any, 0, 4, s), 41);
+  hipLaunchKernelGGL(k_any_active, nbl, dim3(256), 0, s, k.active,
+                     (uint32_t)k.L, k.d_any);
+  uint32_t any = 0;
+  HIP_TRY(c, hipMemcpyAsync(&any, k.d_any, 4, hipMemcpyDeviceToHost, s), 41);
+  HIP_TRY(c, hipStreamSynchronize(s), 41);
+  if (!any) {
+    *p_done = true;
+    return 0;
+  }
+
+  const dim3 nbt(simp_blocks(T)), nbv(simp_blocks(V));
+  const uint64_t NP = 3 * T;
+  uint32_t *faces_g = c->faces.get();
+  float *verts = c->verts.get();
+  uint32_t *flab = c->simp_flab.get();
+  unsigned long long *pick = c->simp_pick.get();
+  uint32_t *remap = c->simp_remap.get();
+  uint32_t *accept = c->simp_accept.get();
+  uint32_t *keep = c->simp_keep.get();
+  uint32_t *keep_scan = c->simp_keep_scan.get();
+  float *Q = c->simp_Q.get();
+
+  hipLaunchKernelGGL(k_face_planes, nbt, blk, 0, s, faces_g, verts, k.active,
+                     flab, c->simp_fq.get(), c->simp_valid.get(), T);
+  hipLaunchKernelGGL(k_emit_vf_pairs, nbt, blk, 0, s, faces_g, k.active, flab,
+                     c->simp_pk.get(), c->simp_pv.get(), T);
+  // stable sort pairs by vertex (face order preserved within vertex)
+  {
+    rocprim::double_buffer<uint32_t> dk(c->simp_pk.get(),
+                                        c->simp_pk_alt.get());
+    rocprim::double_buffer<uint32_t> dv(c->simp_pv.get(),
+                                        c->simp_pv_alt.get());
+    if (int e = sort_pairs(c, dk, dv, NP, 0u, 32u, s,
+                           "simplify sort size query", "simplify sort", 42))
+      return e;
+    hipLaunchKernelGGL(k_accum_quadrics, dim3(simp_blocks(NP)), blk, 0, s,
+                       dk.current(), dv.current(), c->simp_fq.get(),
+                       c->simp_valid.get(), Q, NP);
+  }
+  HIP_TRY(c, hipMemsetAsync(pick, 0xFF, V * 8, s), 43);
+  if (k.env.propose) HIP_TRY(c, hipMemsetAsync(accept, 0xFF, V * 4, s), 43);
+  hipLaunchKernelGGL(k_edge_pick, nbt, blk, 0, s, faces_g, k.active, flab,
+                     c->vbase.get(), verts, Q, pick, k.max_cost, T);
+  hipLaunchKernelGGL(k_iota, nbv, blk, 0, s, remap, V);
+  hipLaunchKernelGGL(k_collapse, nbv, blk, 0, s, pick, verts, remap, Q, V);
+  if (k.env.propose) {
+    hipLaunchKernelGGL(k_propose, nbv, blk, 0, s, pick, accept, V);
+    hipLaunchKernelGGL(k_accept, nbv, blk, 0, s, pick, accept, verts, remap,
+                       Q, V);
+  }
+  hipLaunchKernelGGL(k_remap_faces, nbt, blk, 0, s, faces_g, remap, keep, T);
+  if (int e = scan_u32(c, keep, keep_scan, T, s, "keep scan size query",
+                       "keep scan", 44))
+    return e;
+  uint32_t *d_kept = &c->scalars->simp_kept;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, keep_scan, keep, T,
+                     d_kept);
+  uint32_t kept = 0;
+  HIP_TRY(c, hipMemcpyAsync(&kept, d_kept, 4, hipMemcpyDeviceToHost, s), 44);
+  HIP_TRY(c, hipMemsetAsync(k.nt_new, 0, k.L * 4, s), 44);
+  hipLaunchKernelGGL(k_compact_faces, nbt, blk, 0, s, faces_g, flab, keep,
+                     keep_scan, c->simp_faces_alt.get(),
+                     c->simp_flab_alt.get(), k.nt_new, T);
+  hipLaunchKernelGGL(k_update_active, nbl, dim3(256), 0, s, k.nt_new,
+                     k.nt_cur, k.target, k.active, k.d_any, (uint32_t)k.L,
+                     1u);
+  HIP_TRY(c, hipGetLastError(), 44);
+  HIP_TRY(c, hipStreamSynchronize(s), 44);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->simp_flab, c->simp_flab_alt);
+  *p_T = kept;
+  if (kept == 0) {
+    *p_done = true;
+    return 0;
+  }
+  // park faces of labels that just went inactive: working set keeps
+  // only active labels (late rounds touch only the active tail)
+  return park_inactive(c, k, kept, "park scan size query", "park scan", 47,
+                       p_T);
+}
+
+// Final face array (per-label slices gathered from the park store in
+// label-id order), then drop unreferenced vertices (stable) and
+// re-localize the faces. *p_T / *p_V = the final totals.
+static int simp_finalize(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
+                         uint64_t *p_V) {
+  hipStream_t s = c->stream;
+  const dim3 blk(SIMP_BLK);
+  const uint64_t L = k.L, V = k.V;
+  uint32_t *troff_final = c->simp_troff_final.get();
+  if (int e = scan_u32(c, k.nt_cur, troff_final, L, s,
+                       "final troff scan size", "final troff scan", 49))
+    return e;
+  uint32_t *d_total = &c->scalars->simp_final_tris;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, troff_final,
+                     k.nt_cur, L, d_total);
+  HIP_TRY(c, hipMemcpyAsync(troff_final + L, d_total, 4,
+                            hipMemcpyDeviceToDevice, s), 49);
+  uint32_t final_total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&final_total, d_total, 4, hipMemcpyDeviceToHost,
+                            s), 49);
+  HIP_TRY(c, hipStreamSynchronize(s), 49);
+  const uint64_t T = final_total;
+  if (T > 0)
+    hipLaunchKernelGGL(k_gather_final, dim3(simp_blocks(T)), blk, 0, s,
+                       c->simp_park.get(), c->tri_off.get(), troff_final,
+                       c->faces.get(), c->simp_flab.get(), (uint32_t)L, T);
+  uint32_t *faces_g = c->faces.get();
+  std::swap(c->tri_off, c->simp_troff_final);
+
+  if (ensure(c, c->simp_ref, V + 1)) return 45;
+  if (ensure(c, c->simp_verts_alt, 3 * V + 3)) return 45;
+  if (ensure(c, c->simp_vbase_alt, L + 1)) return 45;
+  uint32_t *ref = c->simp_ref.get();
+  // the weld's scan buffer, free now: NC >= V words (weld_scan_view)
+  uint32_t *newid = c->vtx_scan.get();
+  HIP_TRY(c, hipMemsetAsync(ref, 0, V * 4, s), 45);
+  if (T > 0)
+    hipLaunchKernelGGL(k_mark_ref, dim3(simp_blocks(3 * T)), blk, 0, s,
+                       faces_g, ref, 3 * T);
+  if (int e = scan_u32(c, ref, newid, V, s, "ref scan size query",
+                       "ref scan", 45))
+    return e;
+  uint32_t *d_newV = &c->scalars->simp_new_verts;
+  hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(1), 0, s, newid, ref, V,
+                     d_newV);
+  uint32_t newV = 0;
+  HIP_TRY(c, hipMemcpyAsync(&newV, d_newV, 4, hipMemcpyDeviceToHost, s), 45);
+  HIP_TRY(c, hipStreamSynchronize(s), 45);
+  hipLaunchKernelGGL(k_scatter_verts, dim3(simp_blocks(V)), blk, 0, s,
+                     c->verts.get(), ref, newid, c->simp_verts_alt.get(), V);
+  hipLaunchKernelGGL(k_new_vbase, dim3((uint32_t)((L + 2 + 255) / 256)),
+                     dim3(256), 0, s, c->vbase.get(), newid,
+                     c->simp_vbase_alt.get(), (uint32_t)L, newV);
+  if (T > 0)
+    hipLaunchKernelGGL(k_localize_faces, dim3(simp_blocks(T)), blk, 0, s,
+                       faces_g, newid, c->simp_flab.get(),
+                       c->simp_vbase_alt.get(), c->simp_faces_alt.get(), T);
+  HIP_TRY(c, hipGetLastError(), 46);
+  std::swap(c->faces, c->simp_faces_alt);
+  std::swap(c->verts, c->simp_verts_alt);
+  std::swap(c->vbase, c->simp_vbase_alt);
+  *p_T = T;
+  *p_V = newV;
+  return 0;
+}
+
+// Simplify every label of the welded mesh in the ctx (faces / verts /
+// vbase / tri_off, label per face in lab_sorted). Updates those buffers;
+// p_T/p_V become the post-simplification totals.
+static int run_simplify(mg_ctx *c, uint32_t nlabels,
+                        const uint32_t *lab_sorted,
+                        uint32_t reduction_factor, float max_error,
+                        uint64_t *p_T, uint64_t *p_V) {
+  hipStream_t s = c->stream;
+  uint64_t T = *p_T;
+  if (T == 0 || *p_V == 0) return 0;
+  SimpCall k = {};
+  k.env = read_simp_env();
+  k.L = nlabels;
+  k.V = *p_V;
+  k.max_cost = max_error * max_error;
+  if (int e = simp_alloc(c, k, T)) return e;
+
+  // faces -> global vertex ids, label per face
+  hipLaunchKernelGGL(k_globalize_faces, dim3(simp_blocks(T)), dim3(SIMP_BLK),
+                     0, s, c->faces.get(), lab_sorted, c->vbase.get(),
+                     c->simp_flab.get(), T);
+  hipLaunchKernelGGL(k_init_simplify, dim3((uint32_t)((k.L + 255) / 256)),
+                     dim3(256), 0, s, c->tri_off.get(), k.nt_cur, k.target,
+                     k.active, reduction_factor, (uint32_t)k.L);
+  HIP_TRY(c, hipGetLastError(), 40);
+
+  if (k.env.prof) {
+    k.d_prof = c->scalars->simp_prof;
+    HIP_TRY(c, hipMemsetAsync(k.d_prof, 0, 48, s), 40);
+  }
+  if (k.env.roundhist) {  // groups/subs per label
+    if (ensure(c, c->simp_rh, 176)) return 40;
+    k.d_rh = c->simp_rh.get();
+    HIP_TRY(c, hipMemsetAsync(k.d_rh, 0, 176 * 4, s), 40);
+  }
+  if (int e = simp_launch_labels(c, k)) return e;
+
+  // drop the per-label-kernel labels from the working set; park big
+  // never-active labels (their final faces are their originals)
+  if (int e = park_inactive(c, k, T, "prepark scan size", "prepark scan", 50,
+                            &T))
+    return e;
+
+  bool done = false;
+  for (int group = 0; group < 65536 && !done; ++group)
+    if (int e = simp_global_round(c, k, &T, &done)) return e;
+
+  // any faces still in the working set (round-cap exit): force-park them
+  if (T > 0) {
+    HIP_TRY(c, hipMemsetAsync(k.active, 0, k.L, s), 48);
+    if (int e = park_inactive(c, k, T, "force-park scan size query",
+                              "force-park scan", 48, nullptr))
+      return e;
+  }
+  if (int e = simp_finalize(c, k, &T, p_V)) return e;
+  *p_T = T;
+  return 0;
 }

@@ -19,16 +19,22 @@
 //       per voxel, in place;
 //       (optional, mg_mesh_chunk_filled) fill_holes.hip: hole filling by
 //       union-find rounds, hole volume kept resident for mg_mesh_holes
-//   [1] k_count        wave-per-64-cell-segment triangle counts: one
+//   [1] k_count        wave-per-64-cell-segment item and triangle counts
+//                      (item = one (cell, label) pair): one
 //                      classification per cell, one trip per label
 //                      (+ label hash build)                    -> segcnt
-//   [2] scan           rocPRIM exclusive scan                  -> segoff, T
+//   [2] scan           rocPRIM exclusive scan (u64, both counts)
+//                                                      -> segoff, NI, T
 //   [3] k_emit         classify again, wave prefix, write one 8-B
-//                      record + 4-B label id per triangle in canonical
-//                      global order (count table in LDS)
-//   [4] partition      rocPRIM stable radix-sort by label id + 16-B gather
-//   [5] weld           direct-addressed (edge,side) table: atomicMax(~pos)
-//                      first-seen positions (LDS pre-dedup), bit-packed
+//                      record + 4-B label id per ITEM in canonical
+//                      global order
+//   [4] partition      rocPRIM stable radix-sort of the items by label
+//                      id; scan of the sorted items' triangle counts
+//                      -> itoff; per-label triangle ranges
+//   [5] weld           expand items into triangles (t ascending within
+//                      an item: the per-triangle stream, label by label
+//                      in emit order); direct-addressed (edge,side)
+//                      table of first positions, bit-packed
 //                      first-occurrence flags + word-granular scan ->
 //                      vertex ids, vertex emit, per-label face indices
 //   [6] (optional) per-label quadric simplification (one workgroup per
@@ -398,10 +404,14 @@ __device__ __forceinline__ SegSched xcd_seg_sched(int64_t nseg,
   return ss;
 }
 
-// [1] count: one wave per segment; build label hash; write per-segment count
+// [1] count: one wave per segment; build label hash; write the segment's
+// two counts as one u64, (triangles << 32) | items. An item is one
+// (cell, label) pair, so a lane has popcount(first) of them. Both totals
+// stay below 2^32, so one u64 scan gives both offsets and the halves never
+// carry into each other.
 template <typename T>
 __global__ void k_count(const T *__restrict__ labels, GridDims g,
-                        uint32_t *__restrict__ segcnt, LabelHash lh) {
+                        uint64_t *__restrict__ segcnt, LabelHash lh) {
   __shared__ uint8_t s_cnt[256];
   for (int k = threadIdx.x; k < 256; k += blockDim.x)
     s_cnt[k] = MC_TRI_COUNT[k];
@@ -417,20 +427,24 @@ __global__ void k_count(const T *__restrict__ labels, GridDims g,
     const int64_t cy = row % g.ncy;
     const int64_t cz = row / g.ncy;
     const int64_t cx = segx * WAVE + lane;
+    // a lane has at most 8 items and 8 * MC_MAX_TRIS triangles, a wave
+    // 64 times that: both fit 16 bits, so one u32 reduce carries both
     uint32_t cnt = 0;
     if (cx < g.ncx) {
       T c[8];
       load_corners(labels, g.sx, sxy, cx, cy, cz, c);
       const CellClass k = classify_cell(c);
+      cnt = (uint32_t)__popc(k.first);
       for (uint32_t f = k.first; f; f &= f - 1) {
         const uint32_t i = (uint32_t)__builtin_ctz(f);
-        cnt += s_cnt[k.row(i)];
+        cnt += (uint32_t)s_cnt[k.row(i)] << 16;
         label_insert(lh, (uint64_t)pick_corner(c, i));
       }
     }
     // wave reduce
     uint32_t incl = wave_incl_scan(cnt, lane);
-    if (lane == WAVE - 1) segcnt[seg] = incl;
+    if (lane == WAVE - 1)
+      segcnt[seg] = ((uint64_t)(incl >> 16) << 32) | (incl & 0xffffu);
   }
 }
 
@@ -469,21 +483,26 @@ __device__ __forceinline__ void stage_decode_tables(
   }
 }
 
-// [3] emit: recompute counts, wave prefix, write one 8-B record + the
-// 4-B label id per triangle in canonical global order.
-// 8 waves/SIMD (64 VGPRs, no scratch): the kernel waits on memory, and
-// the compiler's own choice of 67 registers gave up a wave for nothing.
+// [3] emit: classify again, wave prefix of the lanes' item counts, write
+// one 8-B record (t = 0) + the 4-B label id per ITEM — per (cell, label)
+// pair — in canonical global order. All triangles of an item share the
+// cell, the mask, the boundary bits and the label; they differ only in
+// t = 0 .. MC_TRI_COUNT[mask]-1, which the weld puts back (k_weld_first).
+// So the stream that the partition sorts carries every distinct piece of
+// information once, about half as many elements as there are triangles.
+//
+// The order is unchanged: emit writes items in (z, y, x) cell order, and
+// within a cell in first-seen corner order; the stable sort by label id
+// keeps each label's items in cell order (a label has at most one item
+// per cell); expanding each item with t ascending gives, label by label,
+// cells in (z, y, x) order and t ascending within the cell — exactly the
+// stream a stable sort of per-triangle records gave.
+// 8 waves/SIMD (no scratch): the kernel waits on memory.
 template <typename T>
 __global__ __launch_bounds__(256, 8) void k_emit(
     const T *__restrict__ labels, GridDims g,
-    const uint32_t *__restrict__ segoff, LabelHash lh,
-    uint32_t *__restrict__ tri_label, uint2 *__restrict__ tri_recs) {
-  // count table staged in LDS: global-memory byte gathers on the small
-  // case tables were the emit kernel's dominant cost (L1 line replays)
-  __shared__ uint8_t s_cnt[256];
-  for (int k = threadIdx.x; k < 256; k += blockDim.x)
-    s_cnt[k] = MC_TRI_COUNT[k];
-  __syncthreads();
+    const uint64_t *__restrict__ segoff, LabelHash lh,
+    uint32_t *__restrict__ item_label, uint2 *__restrict__ item_recs) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave_in_blk = threadIdx.x / WAVE;
   const int waves_per_blk = blockDim.x / WAVE;
@@ -499,52 +518,73 @@ __global__ __launch_bounds__(256, 8) void k_emit(
     CellClass k;
     k.rows = 0;
     k.first = 0;
-    // per-label triangle counts, 4 bits at 4*i for each first corner i
-    // (MC_MAX_TRIS < 16): one round of LDS lookups serves the prefix sum
-    // and the emit walk
-    uint32_t nts = 0;
-    uint32_t cnt = 0;
     if (cx < g.ncx) {
       load_corners(labels, g.sx, sxy, cx, cy, cz, c);
       k = classify_cell(c);
-      #pragma unroll
-      for (uint32_t i = 0; i < 8; ++i) {
-        const uint32_t nt = (k.first >> i) & 1u ? s_cnt[k.row(i)] : 0u;
-        nts |= nt << (4 * i);
-        cnt += nt;
-      }
     }
+    const uint32_t cnt = (uint32_t)__popc(k.first);  // the lane's items
     uint32_t incl = wave_incl_scan(cnt, lane);
-    uint32_t pos = segoff[seg] + incl - cnt;
+    // low half of the scanned u64 = the segment's item offset
+    uint32_t pos = (uint32_t)segoff[seg] + incl - cnt;
     const uint32_t cell_lin = (uint32_t)((cz * g.sy + cy) * g.sx + cx);
     const uint32_t zero = (uint32_t)(cx == 0) | ((uint32_t)(cy == 0) << 1) |
                           ((uint32_t)(cz == 0) << 2);
     for (uint32_t f = k.first; f; f &= f - 1) {
       const uint32_t i = (uint32_t)__builtin_ctz(f);
-      const uint32_t mask = k.row(i);
-      const uint32_t nt = (nts >> (4 * i)) & 15u;
       const uint32_t lid = label_lookup(lh, (uint64_t)pick_corner(c, i));
-      for (uint32_t t = 0; t < nt; ++t) {
-        tri_label[pos] = lid;
-        tri_recs[pos] = make_uint2(cell_lin, mask | (t << 8) | (zero << 11));
-        ++pos;
-      }
+      item_label[pos] = lid;
+      item_recs[pos] = make_uint2(cell_lin, k.row(i) | (zero << 11));
+      ++pos;
     }
   }
 }
 
-// [4c] per-label triangle ranges (labels sorted, every id present)
-__global__ void k_label_ranges(const uint32_t *__restrict__ lab_sorted,
-                               uint32_t *__restrict__ tri_off,
-                               uint64_t ntris, uint32_t nlabels) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= ntris) return;
-  if (i == 0) {
-    tri_off[lab_sorted[0]] = 0;  // first label's range starts at 0
-    tri_off[nlabels] = (uint32_t)ntris;
-  } else if (lab_sorted[i] != lab_sorted[i - 1]) {
-    tri_off[lab_sorted[i]] = (uint32_t)i;
+// [4b] triangles of one item, the input of the scan that gives itoff
+// (item -> first triangle of the label-partitioned stream): through the
+// sorted records themselves, or through the sort's permutation
+struct ItemTris {
+  __device__ uint32_t operator()(uint2 rec) const {
+    return MC_TRI_COUNT[rec.y & 255u];
   }
+};
+struct ItemTrisVia {
+  const uint2 *recs;
+  __device__ uint32_t operator()(uint32_t o) const {
+    return MC_TRI_COUNT[recs[o].y & 255u];
+  }
+};
+
+// [4c] one thread per sorted ITEM i, which holds triangles
+// [itoff[i], itoff[i+1]) of the stream. itoff[1..nitems] is the inclusive
+// scan of the items' triangle counts; itoff[0] = 0 is stored here.
+//  - per-label triangle ranges (labels sorted, every id present): where
+//    the label changes, tri_off[label] = the item's first triangle
+//  - blk_item[b] = the item that holds triangle b * WELD_FIRST_BLK, the
+//    first item of k_weld_first's block b. An item has at most MC_MAX_TRIS
+//    < WELD_FIRST_BLK triangles, so it holds at most one such triangle,
+//    and every b below ceil(ntris / WELD_FIRST_BLK) is held by some item.
+#define WELD_FIRST_BLK 256
+__global__ void k_label_ranges(const uint32_t *__restrict__ item_lab,
+                               uint32_t *__restrict__ itoff,
+                               uint32_t *__restrict__ tri_off,
+                               uint32_t *__restrict__ blk_item,
+                               uint64_t nitems, uint64_t ntris,
+                               uint32_t nlabels) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nitems) return;
+  uint32_t a = 0;
+  if (i == 0) {
+    itoff[0] = 0;
+    tri_off[item_lab[0]] = 0;  // first label's range starts at 0
+    tri_off[nlabels] = (uint32_t)ntris;
+  } else {
+    a = itoff[i];
+    if (item_lab[i] != item_lab[i - 1]) tri_off[item_lab[i]] = a;
+  }
+  const uint32_t b = itoff[i + 1];
+  // the first block boundary at or after a
+  const uint32_t m = (a + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK;
+  if (m * WELD_FIRST_BLK < b) blk_item[m] = (uint32_t)i;
 }
 
 // ---------------------------------------------------------------------------
@@ -583,30 +623,73 @@ __global__ void k_label_ranges(const uint32_t *__restrict__ lab_sorted,
 // (vertex ids come from a word-granular scan + popcount). A wave's 64
 // triangles are corners [192w, 192w+192) = words 3w..3w+2: three ballots,
 // one per v, re-interleaved into corner order by a second ballot per word.
-#define WELD_FIRST_BLK 256
+//
+// The stream arrives per ITEM (k_emit): the block expands its items into
+// triangles. Its 256 consecutive triangles lie in at most 256 consecutive
+// items, since every item has at least one triangle; the first of them is
+// blk_item[block] (k_label_ranges). Thread i takes item first + i: it
+// stages the item's triangle offset, and if the item reaches into the
+// block, its record and label, and marks the item's triangles of the
+// block with i in LDS. Thread r then finds its triangle's item j there:
+// t_in = t - itoff[j] is the triangle's index within the item, and the
+// record is item j's with t_in in bits 8-10. The per-triangle label array
+// (k_weld_verts_faces, k_vbase and the simplifier read it) is written here.
 __global__ __launch_bounds__(WELD_FIRST_BLK) void k_weld_first(
-    const uint2 *__restrict__ tri_recs,   // 8-B records
+    const uint2 *__restrict__ item_recs,  // 8-B records, one per item
     const uint32_t *__restrict__ order,   // label partition permutation,
                                           // or null: records already sorted
+    const uint32_t *__restrict__ item_lab,  // sorted label id per item
+    const uint32_t *__restrict__ itoff,     // nitems + 1 triangle offsets
+    const uint32_t *__restrict__ blk_item,
+    uint32_t *__restrict__ lab_sorted,    // label id per triangle
     uint32_t *__restrict__ slots_sorted,  // decoded 3 slots/tri (12 B)
     uint32_t *__restrict__ wminp,
     unsigned long long *__restrict__ bits,
     int64_t sx, int64_t sxy,
-    uint64_t ntris, uint64_t nwords) {
+    uint64_t nitems, uint64_t ntris, uint64_t nwords) {
   __shared__ uint16_t s_pack[256 * MC_MAX_TRIS];
   __shared__ uint8_t s_first[256 * MC_MAX_TRIS];
   __shared__ uint32_t s_comb[12];
   __shared__ uint32_t s_need[12];
+  __shared__ uint32_t s_off[WELD_FIRST_BLK + 1];
+  __shared__ uint2 s_rec[WELD_FIRST_BLK];
+  __shared__ uint32_t s_lab[WELD_FIRST_BLK];
+  __shared__ uint8_t s_item[WELD_FIRST_BLK];
   stage_decode_tables(s_pack, s_comb, sx, sxy);
   for (int k = threadIdx.x; k < 256 * MC_MAX_TRIS; k += blockDim.x)
     s_first[k] = MC_TRI_FIRST[k / MC_MAX_TRIS][k % MC_MAX_TRIS];
   if (threadIdx.x < 12) s_need[threadIdx.x] = MC_EDGE_NEED[threadIdx.x];
-  __syncthreads();
   const uint64_t t = (uint64_t)blockIdx.x * WELD_FIRST_BLK + threadIdx.x;
+  const uint32_t t0 = blockIdx.x * WELD_FIRST_BLK;  // < ntris < 2^32
+  // offsets of items first .. first + 256, clamped to itoff[nitems] = ntris
+  const uint64_t first = blk_item[blockIdx.x];
+  const uint64_t it = first + threadIdx.x;
+  s_off[threadIdx.x] = itoff[std::min<uint64_t>(it, nitems)];
+  if (threadIdx.x == 0)
+    s_off[WELD_FIRST_BLK] =
+        itoff[std::min<uint64_t>(first + WELD_FIRST_BLK, nitems)];
+  __syncthreads();
+  {
+    // the item's triangles inside the block (none for items past its end
+    // or past nitems: their range is empty)
+    const uint32_t lo = std::max(s_off[threadIdx.x], t0);
+    const uint32_t hi = std::min<uint32_t>(s_off[threadIdx.x + 1],
+                                           t0 + WELD_FIRST_BLK);
+    if (lo < hi) {
+      s_rec[threadIdx.x] = order ? item_recs[order[it]] : item_recs[it];
+      s_lab[threadIdx.x] = item_lab[it];
+      for (uint32_t q = lo; q < hi; ++q)
+        s_item[q - t0] = (uint8_t)threadIdx.x;
+    }
+  }
+  __syncthreads();
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   bool f[3] = {false, false, false};  // tail lanes contribute 0
   if (t < ntris) {
-    const uint2 rec = order ? tri_recs[order[t]] : tri_recs[t];
+    const uint32_t j = s_item[threadIdx.x];
+    uint2 rec = s_rec[j];
+    rec.y |= ((uint32_t)t - s_off[j]) << 8;  // t within the item
+    lab_sorted[t] = s_lab[j];
     const uint32_t ti = (rec.y & 255u) * MC_MAX_TRIS + ((rec.y >> 8) & 7u);
     const uint32_t pk = s_pack[ti];
     const uint32_t fb = s_first[ti];
@@ -677,7 +760,7 @@ __global__ void k_vbase(const uint32_t *__restrict__ tri_off,
 // are contiguous in the stream, so both that gather and the bits/wscan
 // lookup (12 B per 64 corners) are cache-local.
 // No vertex-id table: faces need nothing the vertex writes produce.
-// Label id from the sorted label array — the partition sort's key output.
+// Label id from the per-triangle label array that k_weld_first wrote.
 __global__ void k_weld_verts_faces(const uint32_t *__restrict__ slots,
                                    const uint32_t *__restrict__ wminp,
                                    const uint32_t *__restrict__ lab_sorted,
@@ -905,15 +988,17 @@ struct ChunkCall {
   float rx, ry, rz;
   int voxel_centered;
   uint32_t nlabels;        // run_count_emit
+  uint64_t NI;             // items = (cell, label) pairs (run_count_emit)
   uint64_t T;              // triangles (run_count_emit; run_simplify)
   uint64_t V;              // vertices (run_weld; run_simplify)
-  // run_partition: label id per triangle (the sort's key output), the
-  // 8-B records the weld reads and the permutation to read them through
+  // run_partition: label id per item (the sort's key output), the 8-B
+  // item records the weld reads and the permutation to read them through
   // (null when the records themselves were sorted), the slot triples
-  uint32_t *lab_sorted;
+  const uint32_t *item_lab;
   const uint2 *rec_src;
   const uint32_t *order_sorted;
   uint32_t *slots;
+  uint32_t *lab_sorted;    // label id per triangle (run_weld writes it)
 };
 
 static void set_hole_stash(mg_ctx *c, const ChunkCall &k) {
@@ -1034,8 +1119,8 @@ static inline uint32_t seg_blocks(const GridDims &g, int blk) {
 static int count_pass(mg_ctx *c, ChunkCall &k, bool *p_overflow) {
   hipStream_t s = c->stream;
   const LabelHash lh = label_hash_view(c);
-  uint32_t *d_segcnt = c->segcnt.get();
-  uint32_t *d_segoff = c->segoff.get();
+  uint64_t *d_segcnt = c->segcnt.get();
+  uint64_t *d_segoff = c->segoff.get();
   const int64_t nseg = k.g.nseg;
   HIP_TRY(c, hipEventRecord(c->ev[EV_H2D_END], s), 30);  // see the enum
   by_dtype(k.dtype, [&](auto t) {
@@ -1051,19 +1136,22 @@ static int count_pass(mg_ctx *c, ChunkCall &k, bool *p_overflow) {
   HIP_TRY(c, hipMemcpyAsync(misc, &c->scalars->lh_counter, 8,
                             hipMemcpyDeviceToHost, s), 30);
   // scan segcnt -> segoff
-  if (int e = scan_u32(c, d_segcnt, d_segoff, (size_t)nseg, s,
+  if (int e = scan_u64(c, d_segcnt, d_segoff, (size_t)nseg, s,
                        "seg scan size query failed", "seg scan failed", 30))
     return e;
-  uint32_t last_off = 0, last_cnt = 0;
-  HIP_TRY(c, hipMemcpyAsync(&last_off, d_segoff + (nseg - 1), 4,
+  uint64_t last_off = 0, last_cnt = 0;  // (triangles << 32) | items
+  HIP_TRY(c, hipMemcpyAsync(&last_off, d_segoff + (nseg - 1), 8,
                             hipMemcpyDeviceToHost, s), 30);
-  HIP_TRY(c, hipMemcpyAsync(&last_cnt, d_segcnt + (nseg - 1), 4,
+  HIP_TRY(c, hipMemcpyAsync(&last_cnt, d_segcnt + (nseg - 1), 8,
                             hipMemcpyDeviceToHost, s), 30);
   HIP_TRY(c, hipEventRecord(c->ev[EV_SCAN_END], s), 30);
   HIP_TRY(c, hipStreamSynchronize(s), 30);
   *p_overflow = misc[1] != 0;
   k.nlabels = misc[0];
-  k.T = (uint64_t)last_off + last_cnt;
+  // NI <= T, and T is held to the corner-index limit (run_count_emit)
+  const uint64_t total = last_off + last_cnt;
+  k.NI = total & 0xffffffffull;
+  k.T = total >> 32;
   return 0;
 }
 
@@ -1098,9 +1186,9 @@ static int run_count_emit(mg_ctx *c, ChunkCall &k) {
   hipLaunchKernelGGL(k_label_values,
                      dim3((uint32_t)((c->lh_slots + 255) / 256)), dim3(256),
                      0, s, lh, c->label_values.get(), c->lh_slots);
-  // [3] emit
-  if (ensure(c, c->tri_label, k.T)) return 18;
-  if (ensure(c, c->tri_keys, k.T)) return 18;
+  // [3] emit, one label id + one record per item
+  if (ensure(c, c->tri_label, k.NI)) return 18;
+  if (ensure(c, c->tri_keys, k.NI)) return 18;
   by_dtype(k.dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(k_emit<T>, dim3(seg_blocks(k.g, 256)), dim3(256), 0, s,
@@ -1113,62 +1201,79 @@ static int run_count_emit(mg_ctx *c, ChunkCall &k) {
 }
 
 struct TriSortView {
-  uint64_t *recs, *recs_alt;  // the 8-B records as the sort's u64 values
-  uint32_t *slots;            // decoded slot triples
+  uint64_t *recs, *recs_alt;  // the 8-B item records as the sort's u64 values
+  uint32_t *slots;            // decoded slot triples, per triangle
 };
 
-// c->keys_sorted (5T u32 for T triangles): [sort alternate of tri_keys,
-// 2T words][slot triples, 3T words]
-static TriSortView tri_sort_view(mg_ctx *c, uint64_t T) {
+// c->keys_sorted (2 NI + 3 T u32 for NI items of T triangles): [sort
+// alternate of tri_keys, 2 NI words][slot triples, 3 T words]
+static TriSortView tri_sort_view(mg_ctx *c, uint64_t NI) {
   return {reinterpret_cast<uint64_t *>(c->tri_keys.get()),
           reinterpret_cast<uint64_t *>(c->keys_sorted.get()),
-          c->keys_sorted.get() + 2 * T};
+          c->keys_sorted.get() + 2 * NI};
 }
 
-// [4] stable partition by label id. Default (MG_SORT_RECS=0 reverts):
-// the 8-B records ride the radix sort as its 64-bit VALUES, so the
-// weld reads them back SEQUENTIALLY instead of paying a
-// random 8-B gather through the permutation.
+// [4] stable partition of the ITEMS by label id, then the items' triangle
+// offsets. Default (MG_SORT_RECS=0 reverts): the 8-B records ride the
+// radix sort as its 64-bit VALUES, so the weld reads them back
+// SEQUENTIALLY instead of paying a random 8-B gather through the
+// permutation.
 static int run_partition(mg_ctx *c, ChunkCall &k) {
   hipStream_t s = c->stream;
-  const uint64_t T = k.T;
+  const uint64_t T = k.T, NI = k.NI;
   const char *sre = getenv("MG_SORT_RECS");
   const bool sort_recs = !(sre && sre[0] == '0');
-  if (ensure(c, c->keys_sorted, 5 * T)) return 19;
-  if (ensure(c, c->tri_label_alt, T)) return 19;
-  const TriSortView tv = tri_sort_view(c, T);
+  if (ensure(c, c->keys_sorted, 2 * NI + 3 * T)) return 19;
+  if (ensure(c, c->tri_label_alt, NI)) return 19;
+  const TriSortView tv = tri_sort_view(c, NI);
   k.slots = tv.slots;
-  const dim3 nb((uint32_t)((T + 255) / 256)), blk(256);
+  const dim3 nb((uint32_t)((NI + 255) / 256)), blk(256);
   unsigned end_bit = 1;
   while ((1u << end_bit) < k.nlabels) ++end_bit;
   rocprim::double_buffer<uint32_t> d_keys(c->tri_label.get(),
                                           c->tri_label_alt.get());
   if (sort_recs) {
     rocprim::double_buffer<uint64_t> d_vals(tv.recs, tv.recs_alt);
-    if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
+    if (int e = sort_pairs(c, d_keys, d_vals, NI, 0u, end_bit, s,
                            "radix_sort size query failed",
                            "radix_sort failed", 19))
       return e;
     k.rec_src = reinterpret_cast<const uint2 *>(d_vals.current());
     k.order_sorted = nullptr;  // records already label-partitioned
   } else {
-    if (ensure(c, c->order, T)) return 19;
-    if (ensure(c, c->order_alt, T)) return 19;
-    hipLaunchKernelGGL(k_iota, nb, blk, 0, s, c->order.get(), T);
+    if (ensure(c, c->order, NI)) return 19;
+    if (ensure(c, c->order_alt, NI)) return 19;
+    hipLaunchKernelGGL(k_iota, nb, blk, 0, s, c->order.get(), NI);
     rocprim::double_buffer<uint32_t> d_vals(c->order.get(),
                                             c->order_alt.get());
-    if (int e = sort_pairs(c, d_keys, d_vals, T, 0u, end_bit, s,
+    if (int e = sort_pairs(c, d_keys, d_vals, NI, 0u, end_bit, s,
                            "radix_sort size query failed",
                            "radix_sort failed", 19))
       return e;
     k.rec_src = c->tri_keys.get();
     k.order_sorted = d_vals.current();
   }
-  k.lab_sorted = d_keys.current();
-  // label ranges
+  k.item_lab = d_keys.current();
+  // itoff[1..NI] = inclusive scan of the sorted items' triangle counts
+  // (itoff[NI] = T); k_label_ranges stores itoff[0]
+  if (ensure(c, c->itoff, NI + 1)) return 19;
+  uint32_t *itoff = c->itoff.get();
+  if (int e = k.order_sorted
+          ? scan_incl_u32(c, rocprim::make_transform_iterator(
+                                 k.order_sorted, ItemTrisVia{k.rec_src}),
+                          itoff + 1, NI, s, "item scan size query failed",
+                          "item scan failed", 19)
+          : scan_incl_u32(c, rocprim::make_transform_iterator(
+                                 k.rec_src, ItemTris{}),
+                          itoff + 1, NI, s, "item scan size query failed",
+                          "item scan failed", 19))
+    return e;
+  // label ranges + the weld blocks' first items
   if (ensure(c, c->tri_off, (uint64_t)k.nlabels + 1)) return 19;
-  hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.lab_sorted,
-                     c->tri_off.get(), T, k.nlabels);
+  if (ensure(c, c->blk_item, (T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK))
+    return 19;
+  hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.item_lab, itoff,
+                     c->tri_off.get(), c->blk_item.get(), NI, T, k.nlabels);
   HIP_TRY(c, hipGetLastError(), 19);
   HIP_TRY(c, hipEventRecord(c->ev[EV_PARTITION_END], s), 19);
   return 0;
@@ -1201,6 +1306,8 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
   }
   if (ensure(c, c->wh_keys, wslots)) return 20;   // wminp
   if (ensure(c, c->vtx_scan, NC)) return 20;
+  if (ensure(c, c->lab_sorted, T)) return 20;
+  k.lab_sorted = c->lab_sorted.get();
   // not cleared: k_weld_first stores every slot that is read afterwards
   uint32_t *wminp = c->wh_keys.get();
   const dim3 nbt((uint32_t)((T + 255) / 256)), blk(256);
@@ -1211,7 +1318,9 @@ static int run_weld(mg_ctx *c, ChunkCall &k) {
   hipLaunchKernelGGL(k_weld_first,
                      dim3((uint32_t)((T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK)),
                      dim3(WELD_FIRST_BLK), 0, s, k.rec_src, k.order_sorted,
-                     k.slots, wminp, bits, k.g.sx, k.g.sx * k.g.sy, T, nwords);
+                     k.item_lab, c->itoff.get(), c->blk_item.get(),
+                     k.lab_sorted, k.slots, wminp, bits, k.g.sx,
+                     k.g.sx * k.g.sy, k.NI, T, nwords);
   if (int e = scan_u32(c, rocprim::make_transform_iterator(bits, PopcWord{}),
                        wscan, nwords, s, "weld scan size query failed",
                        "weld scan failed", 20))

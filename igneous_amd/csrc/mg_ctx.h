@@ -93,13 +93,21 @@ struct DeviceBuffers {
   DevArr<CtxScalars> scalars;
   LabelVolume labels, holes;  // holes: fill_holes' resident hole volume
   DevBuf scan_tmp, sort_tmp;
-  DevArr<uint64_t> lh_keys, label_values;
-  DevArr<uint32_t> lh_vals, segcnt, segoff,
+  DevArr<uint64_t> lh_keys, label_values,
+      segcnt, segoff;  // per segment: (triangles << 32) | items
+  // Between emit and weld the stream is per ITEM, one (cell, label) pair:
+  // tri_label / tri_label_alt (the sort's keys), tri_keys, order /
+  // order_alt and itoff hold NI (+1) elements; lab_sorted, the slot
+  // triples and everything from the weld on are per triangle.
+  DevArr<uint32_t> lh_vals,
       tri_label, tri_label_alt, order, order_alt, tri_off,
+      itoff,        // NI + 1: item -> its first triangle of the stream
+      blk_item,     // first item of each 256-triangle block of the weld
+      lab_sorted,   // label id per triangle (k_weld_first)
       keys_sorted,  // carved: tri_sort_view
       vtx_scan,     // carved: weld_scan_view; simp_finalize's newid
       wh_keys, faces, vbase;
-  DevArr<uint2> tri_keys;  // 8-B triangle records
+  DevArr<uint2> tri_keys;  // 8-B item records
   DevArr<float> verts;
   // simplifier
   DevArr<SimpPlane> simp_fq;
@@ -274,6 +282,29 @@ static int scan_u32(mg_ctx *c, In in, uint32_t *out, size_t n, hipStream_t s,
   return rocprim_two_call(
       c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
         return rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n,
+                                       rocprim::plus<uint32_t>(), s);
+      });
+}
+
+// The same over u64 values (the count pass's packed segment counts).
+static int scan_u64(mg_ctx *c, const uint64_t *in, uint64_t *out, size_t n,
+                    hipStream_t s, const char *err_size, const char *err_run,
+                    int rc) {
+  return rocprim_two_call(
+      c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, uint64_t{0}, n,
+                                       rocprim::plus<uint64_t>(), s);
+      });
+}
+
+// Inclusive plus-scan of n u32 values: out[i] = in[0] + ... + in[i].
+template <typename In>
+static int scan_incl_u32(mg_ctx *c, In in, uint32_t *out, size_t n,
+                         hipStream_t s, const char *err_size,
+                         const char *err_run, int rc) {
+  return rocprim_two_call(
+      c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
+        return rocprim::inclusive_scan(tmp, bytes, in, out, n,
                                        rocprim::plus<uint32_t>(), s);
       });
 }

@@ -40,6 +40,9 @@
 //   [6] (optional) per-label quadric simplification (one workgroup per
 //                      label; global matched-pair rounds for huge labels)
 //   [7] D2H slices + meshset assembly (ctx-owned pinned staging)
+//   [7b] (mg_mesh_chunk_encoded, instead of [7]) encode.hip: shift, boxes
+//       and the precomputed / draco fragment bytes of every label, then
+//       D2H of the blob and the per-label tables
 //
 // Determinism: every kernel's output is a pure function of its inputs —
 // atomics are only used for first-position minima (order-free), hash slot
@@ -1413,13 +1416,24 @@ static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
   return 0;
 }
 
+#include "encode.hip"
+
+// The call's empty result: a meshset, or a blobset for an encoded call.
+static int empty_result(mg_ctx *c, mg_meshset **out, mg_blobset **bout) {
+  return bout ? new_blobset(c, 0, bout) : new_meshset(c, 0, out);
+}
+
+// enc / bout are set together, by mg_mesh_chunk_encoded: the call then ends
+// in run_encode and *bout instead of extract_meshset and *out.
 static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                            int sx, int sy, int sz, int dtype,
                            float rx, float ry, float rz,
                            uint32_t reduction_factor, float max_error,
                            int voxel_centered, uint64_t dust_threshold,
                            uint32_t flags, const mg_label_map *map,
-                           uint32_t fill_level, mg_meshset **out) {
+                           uint32_t fill_level, mg_meshset **out,
+                           const EncParams *enc = nullptr,
+                           mg_blobset **bout = nullptr) {
   ChunkCall k = {};
   k.sx = sx; k.sy = sy; k.sz = sz; k.dtype = dtype;
   k.esize = (dtype == MG_U64) ? 8 : 4;
@@ -1440,7 +1454,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
 
   // trivial empty-cell-grid case
   if (g.nseg == 0) {
-    if (int e = new_meshset(c, 0, out)) return e;
+    if (int e = empty_result(c, out, bout)) return e;
     if (fill_level) set_hole_stash(c, k);  // nothing to mesh there either
     return 0;
   }
@@ -1465,7 +1479,7 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
 
   if (int e = run_count_emit(c, k)) return e;
   if (k.T == 0 || k.nlabels == 0) {
-    if (int e = new_meshset(c, 0, out)) return e;
+    if (int e = empty_result(c, out, bout)) return e;
     HIP_TRY(c, hipStreamSynchronize(s), 14);
     c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
     if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
@@ -1479,7 +1493,11 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
                              max_error, &k.T, &k.V))
       return e;
   HIP_TRY(c, hipEventRecord(c->ev[EV_SIMPLIFY_END], s), 22);
-  if (int e = extract_meshset(c, k, flags, out)) return e;
+  if (enc) {
+    if (int e = run_encode(c, k, flags, *enc, bout)) return e;
+  } else {
+    if (int e = extract_meshset(c, k, flags, out)) return e;
+  }
   HIP_TRY(c, hipEventRecord(c->ev[EV_END], s), 25);
   HIP_TRY(c, hipStreamSynchronize(s), 25);
 
@@ -1490,7 +1508,8 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
   c->stats.ms_partition = ev_ms(c, EV_EMIT_END, EV_PARTITION_END);
   c->stats.ms_weld = ev_ms(c, EV_PARTITION_END, EV_WELD_END);
   c->stats.ms_simplify = ev_ms(c, EV_WELD_END, EV_SIMPLIFY_END);
-  c->stats.ms_d2h = ev_ms(c, EV_SIMPLIFY_END, EV_END);
+  c->stats.ms_d2h = ev_ms(c, enc ? EV_ENCODE_END : EV_SIMPLIFY_END, EV_END);
+  if (enc) c->stats.ms_encode = ev_ms(c, EV_SIMPLIFY_END, EV_ENCODE_END);
   c->stats.ms_total = ev_ms(c, EV_START, EV_END);
   if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
   return 0;
@@ -1552,14 +1571,16 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
 
 #include "chunk_mesh.hip"
 
-extern "C" {
-
-int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
-                         int sz, int dtype, float rx, float ry, float rz,
-                         uint32_t reduction_factor, float max_error,
-                         int voxel_centered, uint64_t dust_threshold,
-                         uint32_t flags, const mg_label_map *map,
-                         uint32_t fill_level, mg_meshset **out) {
+// mg_mesh_chunk_filled and mg_mesh_chunk_encoded: argument checks, then
+// mesh_chunk_impl. ep / bout belong to the encoded call (encoded = true).
+static int mesh_chunk_checked(mg_ctx *c, const void *labels, int sx, int sy,
+                              int sz, int dtype, float rx, float ry, float rz,
+                              uint32_t reduction_factor, float max_error,
+                              int voxel_centered, uint64_t dust_threshold,
+                              uint32_t flags, const mg_label_map *map,
+                              uint32_t fill_level, mg_meshset **out,
+                              bool encoded, const mg_encode_params *ep,
+                              mg_blobset **bout) {
   if (!c) { SET_ERR(c, "null ctx"); return 1; }
   std::lock_guard<std::mutex> g(c->lock);
   c->err.clear();
@@ -1573,7 +1594,13 @@ int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
             "resident volume is already filled)");
     return 6;
   }
-  if (!labels || !out) { SET_ERR(c, "null argument"); return 1; }
+  if (!labels || (encoded ? !bout : !out)) {
+    SET_ERR(c, "null argument");
+    return 1;
+  }
+  EncParams enc;
+  if (encoded)
+    if (int e = check_encode_params(c, ep, &enc)) return e;
   c->holes_valid = false;  // a stash belongs to the call just before
   if (int e = check_volume_args(c, sx, sy, sz, dtype)) return e;
   if (map)
@@ -1581,8 +1608,38 @@ int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return mesh_chunk_impl(c, labels, sx, sy, sz, dtype, rx, ry, rz,
                          reduction_factor, max_error, voxel_centered,
-                         dust_threshold, flags, map, fill_level, out);
+                         dust_threshold, flags, map, fill_level, out,
+                         encoded ? &enc : nullptr, encoded ? bout : nullptr);
 }
+
+extern "C" {
+
+int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
+                         int sz, int dtype, float rx, float ry, float rz,
+                         uint32_t reduction_factor, float max_error,
+                         int voxel_centered, uint64_t dust_threshold,
+                         uint32_t flags, const mg_label_map *map,
+                         uint32_t fill_level, mg_meshset **out) {
+  return mesh_chunk_checked(c, labels, sx, sy, sz, dtype, rx, ry, rz,
+                            reduction_factor, max_error, voxel_centered,
+                            dust_threshold, flags, map, fill_level, out,
+                            false, nullptr, nullptr);
+}
+
+int mg_mesh_chunk_encoded(mg_ctx *c, const void *labels, int sx, int sy,
+                          int sz, int dtype, float rx, float ry, float rz,
+                          uint32_t reduction_factor, float max_error,
+                          int voxel_centered, uint64_t dust_threshold,
+                          uint32_t flags, const mg_label_map *map,
+                          const mg_encode_params *params, mg_blobset **out) {
+  return mesh_chunk_checked(c, labels, sx, sy, sz, dtype, rx, ry, rz,
+                            reduction_factor, max_error, voxel_centered,
+                            dust_threshold, flags, map, 0u, nullptr, true,
+                            params, out);
+}
+
+// the blob is ctx-owned (pinned, reused); this frees the descriptor
+void mg_blobset_free(mg_blobset *bs) { free(bs); }
 
 int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
                          int sz, int dtype, float rx, float ry, float rz,

@@ -2,6 +2,7 @@
 // shares. Included at the top of meshgine.hip (single TU).
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -136,6 +137,12 @@ struct DeviceBuffers {
       cm_cells,  // carved: CM_CELL_FIELDS arrays of one stride
       cm_wkey, cm_wkey_alt, cm_wval, cm_wval_alt, cm_whead, cm_wrun,
       cm_head_pos, cm_rep, cm_keep, cm_used, cm_vid, cm_fslot, cm_out_f;
+  // encode (encode.hip): per-label entry sizes / offsets / varint index
+  // bytes, box words (order-preserving u32) and boxes (f32), the blob
+  DevArr<uint64_t> enc_size, enc_off, enc_ilen;
+  DevArr<uint32_t> enc_box;
+  DevArr<float> enc_bbox;
+  DevArr<uint8_t> enc_blob;
 };
 
 // Timing / ordering events of one mesh_chunk_impl call. EV_H2D_END is
@@ -159,6 +166,7 @@ enum {
   EV_MAP_END,
   EV_FILL_START,
   EV_FILL_END,
+  EV_ENCODE_END,    // after the encode kernels (mg_mesh_chunk_encoded)
   EV_COUNT_
 };
 
@@ -177,6 +185,7 @@ struct mg_ctx : DeviceBuffers {
   // pinned output staging, reused across calls
   HostArr<float> h_verts;
   HostArr<uint32_t> h_faces;
+  HostArr<uint8_t> h_blob;  // mg_mesh_chunk_encoded's blob, sized in bytes
   hipEvent_t ev[EV_COUNT_] = {};
 
   // release order: device buffers, pinned buffers, events, stream2, stream
@@ -185,6 +194,7 @@ struct mg_ctx : DeviceBuffers {
     static_cast<DeviceBuffers &>(*this) = DeviceBuffers();  // frees each
     h_verts.release();
     h_faces.release();
+    h_blob.release();
     for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     if (stream2) (void)hipStreamDestroy(stream2);
     if (stream) (void)hipStreamDestroy(stream);

@@ -35,7 +35,9 @@ _EXPORTED_SYMBOLS = [
     "mg_mesh_chunk_filled", "mg_mesh_holes", "mg_fill_holes",
     "mg_simplify_mesh", "mg_chunk_mesh", "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
+    "mg_mesh_chunk_encoded", "mg_blobset_free",
 ]
+MG_ENC_PRECOMPUTED, MG_ENC_DRACO = 0, 1
 
 
 class _MgMesh(ctypes.Structure):
@@ -108,6 +110,125 @@ class MgStatsFill(MgStats):
     ]
 
 
+class MgStatsEncode(MgStatsFill):
+    """... and ms_encode behind ms_fill (mg_mesh_chunk_encoded)."""
+    _fields_ = [
+        ("ms_encode", ctypes.c_double),
+    ]
+
+
+class _MgEncodeParams(ctypes.Structure):
+    _fields_ = [
+        ("format", ctypes.c_uint32),
+        ("shift", ctypes.c_float * 3),
+        ("q_origin", ctypes.c_double * 3),
+        ("q_range", ctypes.c_double),
+        ("q_bits", ctypes.c_uint32),
+    ]
+
+
+class _MgBlobSet(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint32),
+        ("labels", ctypes.POINTER(ctypes.c_uint64)),
+        ("offset", ctypes.POINTER(ctypes.c_uint64)),
+        ("size", ctypes.POINTER(ctypes.c_uint64)),
+        ("nverts", ctypes.POINTER(ctypes.c_uint32)),
+        ("ntris", ctypes.POINTER(ctypes.c_uint32)),
+        ("bbox", ctypes.POINTER(ctypes.c_float)),
+        ("blob", ctypes.POINTER(ctypes.c_uint8)),
+        ("blob_bytes", ctypes.c_uint64),
+    ]
+
+
+class EncodedChunk:
+    """Every label's finished fragment of one chunk (mg_blobset): the
+    bytes MeshTask uploads and the box its spatial index stores.
+
+    labels (ascending u64), offsets / sizes (u64, into blob), nverts /
+    ntris (u32) and bboxes (n x 6 f32: min x, y, z, max x, y, z) are
+    parallel arrays; blob is one uint8 array. len() is the number of
+    labels, chunk[label] that label's bytes (KeyError if absent),
+    chunk.bbox(label) its box, items() yields (label, bytes, box) in
+    ascending label order. The bytes objects own their storage; blob
+    itself may be a view of the engine's staging (copy=False), valid
+    until the next call on that Engine."""
+
+    def __init__(self, labels, offsets, sizes, nverts, ntris, bboxes, blob):
+        self.labels = np.asarray(labels, dtype=np.uint64)
+        self.offsets = np.asarray(offsets, dtype=np.uint64)
+        self.sizes = np.asarray(sizes, dtype=np.uint64)
+        self.nverts = np.asarray(nverts, dtype=np.uint32)
+        self.ntris = np.asarray(ntris, dtype=np.uint32)
+        self.bboxes = np.asarray(bboxes, dtype=np.float32).reshape(-1, 6)
+        self.blob = np.asarray(blob, dtype=np.uint8)
+        n = self.labels.shape[0]
+        for name in ("offsets", "sizes", "nverts", "ntris", "bboxes"):
+            if getattr(self, name).shape[0] != n:
+                raise ValueError(f"EncodedChunk: {name} does not have one "
+                                 f"entry per label")
+        if n and np.any(self.labels[1:] <= self.labels[:-1]):
+            raise ValueError("EncodedChunk: labels must be ascending")
+        if n and int((self.offsets + self.sizes).max()) > self.blob.shape[0]:
+            raise ValueError("EncodedChunk: an entry ends past the blob")
+
+    def __len__(self) -> int:
+        return int(self.labels.shape[0])
+
+    def _index(self, label) -> int:
+        label = int(label)
+        if 0 <= label < (1 << 64):
+            i = int(np.searchsorted(self.labels, np.uint64(label)))
+            if i < len(self) and int(self.labels[i]) == label:
+                return i
+        raise KeyError(label)
+
+    def __contains__(self, label) -> bool:
+        try:
+            self._index(label)
+        except KeyError:
+            return False
+        return True
+
+    def _bytes(self, i: int) -> bytes:
+        o = int(self.offsets[i])
+        return self.blob[o:o + int(self.sizes[i])].tobytes()
+
+    def __getitem__(self, label) -> bytes:
+        return self._bytes(self._index(label))
+
+    def bbox(self, label) -> list:
+        return self.bboxes[self._index(label)].tolist()
+
+    def items(self):
+        boxes = self.bboxes.tolist()
+        for i, label in enumerate(self.labels.tolist()):
+            yield label, self._bytes(i), boxes[i]
+
+
+def _draco_numbers(draco):
+    """(origin[3], range, bits) as formats.draco.encode's float path ends
+    up using them — its own defaulting applied, so the device sees final
+    numbers. Per-mesh defaults (origin / range from each mesh's own
+    extent) are not a per-chunk setting and are refused."""
+    if draco is None:
+        raise ValueError("encoding='draco' needs the draco settings "
+                         "(quantization_bits / _range / _origin)")
+    if draco.get("quantization_origin") is None \
+            or draco.get("quantization_range") is None:
+        raise ValueError("draco: quantization_origin and quantization_range "
+                         "must be given (MeshTask's draco_encoding_settings "
+                         "always sets them)")
+    origin = np.asarray(draco["quantization_origin"], dtype=np.float64)
+    if origin.shape != (3,):
+        raise ValueError("draco: quantization_origin must have 3 components")
+    rng = float(np.max(draco["quantization_range"]))
+    if rng <= 0:
+        rng = 1.0
+    bits = int(draco.get("quantization_bits", 14))
+    return [float(x) for x in origin], rng, bits
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -149,6 +270,12 @@ def load_library() -> ctypes.CDLL:
             lib.mg_mesh_chunk.argtypes[:-1]
             + [ctypes.POINTER(_MgLabelMap), ctypes.c_uint32]
             + lib.mg_mesh_chunk.argtypes[-1:])
+        lib.mg_mesh_chunk_encoded.restype = ctypes.c_int
+        lib.mg_mesh_chunk_encoded.argtypes = (
+            lib.mg_mesh_chunk.argtypes[:-1]
+            + [ctypes.POINTER(_MgLabelMap), ctypes.POINTER(_MgEncodeParams),
+               ctypes.POINTER(ctypes.POINTER(_MgBlobSet))])
+        lib.mg_blobset_free.argtypes = [ctypes.POINTER(_MgBlobSet)]
         lib.mg_mesh_holes.restype = ctypes.c_int
         lib.mg_mesh_holes.argtypes = [
             ctypes.c_void_p,
@@ -166,7 +293,7 @@ def load_library() -> ctypes.CDLL:
         lib.mg_meshset_free.argtypes = [ctypes.POINTER(_MgMeshSet)]
         lib.mg_get_stats.restype = ctypes.c_int
         lib.mg_get_stats.argtypes = [ctypes.c_void_p,
-                                     ctypes.POINTER(MgStatsFill)]
+                                     ctypes.POINTER(MgStatsEncode)]
         lib.mg_last_error.restype = ctypes.c_char_p
         lib.mg_last_error.argtypes = [ctypes.c_void_p]
         lib.mg_device_count.restype = ctypes.c_int
@@ -313,24 +440,7 @@ class Engine:
             float(resolution[0]), float(resolution[1]), float(resolution[2]),
             int(reduction_factor), float(max_error),
             int(bool(voxel_centered)), int(dust_threshold), flags)
-        cmap = None
-        if label_map is not None:
-            if skip_h2d:
-                raise ValueError(
-                    "label_map cannot be combined with skip_h2d: the "
-                    "resident volume has already been mapped")
-            keys, vals, miss = label_map
-            if miss not in ('keep', 'zero'):
-                raise ValueError(f"label_map miss policy {miss!r}: "
-                                 f"expected 'keep' or 'zero'")
-            keys = np.ascontiguousarray(keys, dtype=np.uint64)
-            vals = np.ascontiguousarray(vals, dtype=np.uint64)
-            if keys.ndim != 1 or keys.shape != vals.shape:
-                raise ValueError("label_map keys/vals must be 1-D arrays "
-                                 "of equal length")
-            cmap = _MgLabelMap(
-                keys.ctypes.data, vals.ctypes.data, keys.shape[0],
-                MG_MAP_MISS_ZERO if miss == 'zero' else MG_MAP_MISS_KEEP)
+        cmap, _keep = self._label_map_struct(label_map, skip_h2d)
         with self._lock:
             out = ctypes.POINTER(_MgMeshSet)()
             if fill_holes:
@@ -356,6 +466,113 @@ class Engine:
                 ctypes.byref(out))
             self._check(rc, "mg_mesh_holes")
             return result, self._collect(out, True)
+
+    @staticmethod
+    def _label_map_struct(label_map, skip_h2d: bool):
+        """(mg_label_map or None, the arrays it points into)."""
+        if label_map is None:
+            return None, None
+        if skip_h2d:
+            raise ValueError(
+                "label_map cannot be combined with skip_h2d: the "
+                "resident volume has already been mapped")
+        keys, vals, miss = label_map
+        if miss not in ('keep', 'zero'):
+            raise ValueError(f"label_map miss policy {miss!r}: "
+                             f"expected 'keep' or 'zero'")
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        if keys.ndim != 1 or keys.shape != vals.shape:
+            raise ValueError("label_map keys/vals must be 1-D arrays "
+                             "of equal length")
+        cmap = _MgLabelMap(
+            keys.ctypes.data, vals.ctypes.data, keys.shape[0],
+            MG_MAP_MISS_ZERO if miss == 'zero' else MG_MAP_MISS_KEEP)
+        return cmap, (keys, vals)
+
+    def mesh_chunk_encoded(self, labels: np.ndarray,
+                           resolution=(1.0, 1.0, 1.0),
+                           reduction_factor: int = 0,
+                           max_error: float = 40.0,
+                           voxel_centered: bool = True,
+                           dust_threshold: int = 0,
+                           label_map=None,
+                           shift=(0.0, 0.0, 0.0),
+                           encoding: str = 'precomputed',
+                           draco=None,
+                           device_only: bool = False,
+                           copy: bool = True,
+                           skip_h2d: bool = False) -> EncodedChunk:
+        """mesh_chunk, ending in every label's finished fragment instead
+        of its mesh (mg_mesh_chunk_encoded): for each label, the bytes and
+        box MeshTask's host loop makes from mesh_chunk's result for the
+        same arguments — vertices + shift (three f32), their min/max, and
+        Mesh.to_precomputed() or formats.draco.encode(**draco) — computed
+        on the device, byte for byte.
+
+        encoding='draco' takes draco = the settings dict of
+        tasks.draco.draco_encoding_settings (quantization_bits / _range /
+        _origin; other keys are ignored, as the encoder ignores them).
+        copy=False leaves the blob a view of this context's pinned
+        staging, valid until the next call on this Engine. Under
+        device_only the set is empty (stats still filled)."""
+        if encoding not in ('precomputed', 'draco'):
+            raise ValueError(f"encoding {encoding!r}: expected "
+                             f"'precomputed' or 'draco'")
+        params = _MgEncodeParams()
+        params.format = (MG_ENC_DRACO if encoding == 'draco'
+                         else MG_ENC_PRECOMPUTED)
+        shift = np.asarray(shift, dtype=np.float32).reshape(3)
+        params.shift[:] = [float(x) for x in shift]
+        if encoding == 'draco':
+            origin, rng, bits = _draco_numbers(draco)
+            params.q_origin[:] = origin
+            params.q_range = rng
+            if not 0 <= bits < (1 << 32):
+                raise ValueError(f"draco: quantization_bits {bits}")
+            params.q_bits = bits
+        labels = np.asfortranarray(labels)
+        dtype = _mg_dtype(labels)
+        sx, sy, sz = labels.shape
+        flags = (MG_FLAG_DEVICE_ONLY if device_only else 0) | \
+                (MG_FLAG_SKIP_H2D if skip_h2d else 0)
+        cmap, _keep = self._label_map_struct(label_map, skip_h2d)
+        with self._lock:
+            out = ctypes.POINTER(_MgBlobSet)()
+            rc = self.lib.mg_mesh_chunk_encoded(
+                self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
+                sx, sy, sz, dtype,
+                float(resolution[0]), float(resolution[1]),
+                float(resolution[2]),
+                int(reduction_factor), float(max_error),
+                int(bool(voxel_centered)), int(dust_threshold), flags,
+                ctypes.byref(cmap) if cmap is not None else None,
+                ctypes.byref(params), ctypes.byref(out))
+            self._check(rc, "mg_mesh_chunk_encoded")
+            try:
+                bs = out.contents
+                n = int(bs.n)
+                nb = int(bs.blob_bytes)
+
+                def table(ptr, width=None):
+                    if not n:
+                        return np.zeros((0,) if width is None else (0, width),
+                                        dtype=ptr._type_)
+                    shape = (n,) if width is None else (n, width)
+                    return np.ctypeslib.as_array(ptr, shape=shape).copy()
+
+                if nb:
+                    blob = np.ctypeslib.as_array(bs.blob, shape=(nb,))
+                    if copy:
+                        blob = blob.copy()
+                else:
+                    blob = np.zeros(0, dtype=np.uint8)
+                return EncodedChunk(
+                    table(bs.labels), table(bs.offset), table(bs.size),
+                    table(bs.nverts), table(bs.ntris), table(bs.bbox, 6),
+                    blob)
+            finally:
+                self.lib.mg_blobset_free(out)
 
     def _collect(self, out, copy: bool) -> dict:
         """Meshset descriptor -> {label: (verts, faces)}; frees it."""
@@ -494,7 +711,7 @@ class Engine:
         return result
 
     def stats(self) -> dict:
-        s = MgStatsFill()
+        s = MgStatsEncode()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
         if rc != 0:
             raise RuntimeError("mg_get_stats failed")
@@ -526,6 +743,36 @@ mesh_chunk.handles_label_map = True
 # ... and fill_holes levels 1-2 (device volume pass after dust and the
 # label map; the call then returns (filled_meshes, hole_meshes))
 mesh_chunk.handles_fill_holes = True
+
+
+def mesh_chunk_encoded(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
+                       reduction_factor: int = 0, max_error: float = 40.0,
+                       voxel_centered: bool = True,
+                       device_id: Optional[int] = None,
+                       dust_threshold: int = 0, label_map=None,
+                       shift=(0.0, 0.0, 0.0), encoding: str = 'precomputed',
+                       draco=None, copy: bool = True) -> EncodedChunk:
+    """Module-level encoded mesher: see Engine.mesh_chunk_encoded."""
+    if device_id is None:
+        device_id = _default_device()
+    return Engine.get(device_id).mesh_chunk_encoded(
+        labels, resolution, reduction_factor, max_error, voxel_centered,
+        dust_threshold=dust_threshold, label_map=label_map, shift=shift,
+        encoding=encoding, draco=draco, copy=copy)
+
+
+# ... and that it can return the finished fragments instead of meshes:
+# MeshTask calls encode_chunk for a chunk without fill_holes or dry_run and
+# skips its per-label shift / box / encode loop. encode_chunk.formats names
+# the encodings for which the task takes that path by default: a format is
+# listed when the device path beat the host loop by more than three times
+# the host loop's own max-min on EVERY row of tools/probe_encode.py
+# (DESIGN.md §4). draco did; precomputed missed the margin on one row
+# (simplification_factor=100: 31.4 ms gained, 33.8 ms asked), so it keeps
+# the host loop until a probe says otherwise. The call itself serves both:
+# assign ('precomputed', 'draco') here to hand both over.
+mesh_chunk.encode_chunk = mesh_chunk_encoded
+mesh_chunk_encoded.formats = ('draco',)
 
 
 def fill_holes(labels: np.ndarray, level: int = 1,

@@ -22,6 +22,10 @@ handles_label_map. fill_holes levels 1-2 (mesh.py:211-243) ride it too when
 the mesher advertises handles_fill_holes: the fill runs on the device after
 dust and the label selection, the call returns the filled volume's meshes
 and the hole volume's meshes, and the two are concatenated per segment id.
+The per-label loop after the mesher (shift, box, encode — encode_fragment
+below) rides the call as well when the mesher advertises encode_chunk for
+the task's encoding: the engine returns every label's finished bytes and
+box (mg_mesh_chunk_encoded) and the task only uploads them.
 There is no CPU fallback; a missing engine raises.
 
 Deliberate deviations (documented in DESIGN.md):
@@ -66,6 +70,26 @@ def _get_mesher():
         return _mesher_fn
     from .. import engine
     return engine.mesh_chunk
+
+
+def encode_fragment(mesh: Mesh, shift, encoding: str, draco_settings=None):
+    """One label's step of the host loop: shift the mesh's vertices IN
+    PLACE into global nm, take their box, encode. -> (bytes, box), box the
+    flat [minx,miny,minz,maxx,maxy,maxz] of Bbox.to_list() (mesh.py:257).
+
+    This is the contract of the engine's device encode stage
+    (mg_mesh_chunk_encoded gives the same bytes and an == box for every
+    label); the fallback loop and the tests' checker both call it."""
+    mesh.vertices[:] += shift
+    mesh_bounds = (np.amin(mesh.vertices, axis=0).tolist()
+                   + np.amax(mesh.vertices, axis=0).tolist())
+    if encoding == 'draco':
+        # mesh.py:442-446 via our draco restatement (formats/draco.py)
+        from ..formats import draco as draco_fmt
+        binary = draco_fmt.encode(
+            mesh.vertices, mesh.faces, **draco_settings)
+        return binary, mesh_bounds
+    return mesh.to_precomputed(), mesh_bounds
 
 
 class MeshTask(RegisteredTask):
@@ -236,16 +260,56 @@ class MeshTask(RegisteredTask):
         data = data[..., 0]
 
         mesher = _get_mesher()
-        # copy=False where supported: this task consumes (shifts, encodes,
-        # uploads) every mesh before its next engine call, so zero-copy
-        # views into the engine's staging buffers are safe — EXCEPT under
-        # dry_run, where the meshes are handed back to the caller and must
-        # own their storage (the reference returns owned arrays).
         extra = {}
         if device_dust:
             extra['dust_threshold'] = device_dust
         if label_map is not None:
             extra['label_map'] = label_map
+
+        # A mesher that advertises encode_chunk returns every label's
+        # finished bytes and box from one call (the engine's device encode
+        # stage) — no Mesh per label, no host loop. Not with fill_holes
+        # (filled and hole meshes are concatenated on the host) nor under
+        # dry_run (the caller wants the meshes).
+        encode_chunk = getattr(mesher, 'encode_chunk', None)
+        if (encode_chunk is not None and fill_level == 0
+                and not opts['dry_run']
+                and opts['encoding'] in getattr(
+                    encode_chunk, 'formats', (opts['encoding'],))):
+            draco = None
+            if opts['encoding'] == 'draco':
+                draco = dict(self.draco_encoding_settings)
+                # arrives as a numpy float (np.ceil)
+                draco['quantization_bits'] = int(draco['quantization_bits'])
+            encoded = encode_chunk(
+                data,
+                resolution=tuple(float(r) for r in self._volume.resolution),
+                reduction_factor=int(opts['simplification_factor'] or 0),
+                max_error=float(opts['max_simplification_error']),
+                voxel_centered=True,
+                shift=self._global_shift(left_offset),
+                encoding=opts['encoding'],
+                draco=draco,
+                copy=False,
+                **extra,
+            )
+            # a label without vertices: the host loop decides what happens
+            # (np.amin raises on it today), so the chunk goes that way
+            if not np.any(np.asarray(encoded.nverts) == 0):
+                del data
+                binaries = {}
+                bounding_boxes = {}
+                for segid, binary, box in encoded.items():
+                    binaries[segid] = binary
+                    bounding_boxes[segid] = box
+                self._upload(binaries, bounding_boxes)
+                return
+
+        # copy=False where supported: this task consumes (shifts, encodes,
+        # uploads) every mesh before its next engine call, so zero-copy
+        # views into the engine's staging buffers are safe — EXCEPT under
+        # dry_run, where the meshes are handed back to the caller and must
+        # own their storage (the reference returns owned arrays).
         if fill_level:
             # after dust and the label handling above, host or device
             # (mesh.py:193-228); the mesher returns (filled, holes)
@@ -297,7 +361,10 @@ class MeshTask(RegisteredTask):
 
         if opts['dry_run']:
             return (meshes, bounding_boxes)
+        self._upload(binaries, bounding_boxes)
 
+    def _upload(self, binaries, bounding_boxes):
+        opts = self.options
         if opts['sharded']:
             self._upload_batch(binaries, self._bounds)
         else:
@@ -367,22 +434,18 @@ class MeshTask(RegisteredTask):
             data, list(remap_table.keys()), in_place=True)
         return fastremap_np.remap(data, remap_table, in_place=True)
 
-    def _create_mesh_binary(self, mesh: Mesh, left_bound_offset):
+    def _global_shift(self, left_bound_offset):
+        """Chunk-local nm -> global nm (mesh.py:434-435), three f32."""
         resolution = self._volume.resolution
         offset = (self._bounds.minpt - self.options['low_padding']).astype(np.float32)
-        mesh.vertices[:] += (
-            (offset - np.asarray(left_bound_offset, dtype=np.float32))
-            * np.asarray(resolution, dtype=np.float32))
-        # flat [minx,miny,minz,maxx,maxy,maxz] like Bbox.to_list() (mesh.py:257)
-        mesh_bounds = (np.amin(mesh.vertices, axis=0).tolist()
-                       + np.amax(mesh.vertices, axis=0).tolist())
-        if self.options['encoding'] == 'draco':
-            # mesh.py:442-446 via our draco restatement (formats/draco.py)
-            from ..formats import draco as draco_fmt
-            binary = draco_fmt.encode(
-                mesh.vertices, mesh.faces, **self.draco_encoding_settings)
-            return binary, mesh_bounds
-        return mesh.to_precomputed(), mesh_bounds
+        return ((offset - np.asarray(left_bound_offset, dtype=np.float32))
+                * np.asarray(resolution, dtype=np.float32))
+
+    def _create_mesh_binary(self, mesh: Mesh, left_bound_offset):
+        return encode_fragment(
+            mesh, self._global_shift(left_bound_offset),
+            self.options['encoding'],
+            getattr(self, 'draco_encoding_settings', None))
 
     def _upload_batch(self, mesh_binaries, bbox: Bbox):
         """Sharded fragment output (reference mesh.py:385-397): all the

@@ -40,13 +40,21 @@
  *   mg_chunk_mesh      — replaces zmesh.chunk_mesh in the multires merge
  *                        (multires.py:550,574): grid partition of one mesh
  *                        with clipping at the cell boundaries.
+ *   mg_mesh_chunk_encoded — mg_mesh_chunk_mapped plus the per-label loop
+ *                        that follows it in MeshTask: the shift into
+ *                        global nm (mesh.py:434-435), the spatial-index
+ *                        box, and mesh.to_precomputed (mesh.py:448) or
+ *                        DracoPy.encode (mesh.py:442-446). Returns every
+ *                        label's finished bytes and box.
  *   mg_meshset_free    — replaces Python GC of zmesh.Mesh objects.
  *   mg_last_error      — error text for the last failed call on this ctx.
  *
  * The caller (igneous_amd.tasks.MeshTask, via ctypes) keeps everything the
  * reference keeps in Python: download, padding, folding the
- * remap/object-id options into an mg_label_map, the shift of vertices into global nm coordinates
- * (mesh.py:434-435), precomputed encoding (mesh.py:448) and upload.
+ * remap/object-id options into an mg_label_map, and upload. The shift of
+ * vertices into global nm coordinates (mesh.py:434-435) and the
+ * precomputed / draco encoding (mesh.py:442-448) stay there too for
+ * mg_mesh_chunk*; mg_mesh_chunk_encoded takes them to the device.
  *
  * Vertices returned are CHUNK-LOCAL nm coordinates (float32), exactly as
  * zmesh returns them to MeshTask before the Python-side offset is applied.
@@ -141,7 +149,43 @@ typedef struct {
   double ms_fill;       /* fill_holes: label ids + rounds + hole volume,
                            after the label map and before pass 1 (0 without
                            fill; also inside ms_total) */
+  double ms_encode;     /* mg_mesh_chunk_encoded: the encode kernels, after
+                           the simplifier (0 for every other call; also
+                           inside ms_total). ms_d2h is then the download of
+                           the blob and the per-label tables. */
 } mg_stats;
+
+/* Fragment encoding on the device (mg_mesh_chunk_encoded). The numbers are
+ * final: the caller has applied formats/draco.py's own defaulting. */
+#define MG_ENC_PRECOMPUTED 0u  /* u32 nv | 3*nv f32 | 3*nf u32 */
+#define MG_ENC_DRACO       1u  /* formats/draco.py encode, float path */
+typedef struct {
+  uint32_t format;       /* MG_ENC_* */
+  float    shift[3];     /* added to every vertex, one f32 add each */
+  double   q_origin[3];  /* draco only: quantization origin */
+  double   q_range;      /* draco only: quantization range, > 0 */
+  uint32_t q_bits;       /* draco only: 1..32 */
+} mg_encode_params;
+
+/* Every label's finished fragment. Entry i (labels ascending) is the
+ * size[i] bytes at blob + offset[i]; entries do not overlap and lie in the
+ * blob in an order of the engine's choosing. bbox holds
+ * [min x, min y, min z, max x, max y, max z] of the shifted vertices per
+ * entry. A label without vertices has size 0 and a zero box. The blob is
+ * CTX-OWNED pinned staging under the meshset's lifetime rule (valid until
+ * the next call on the ctx); the tables live in the descriptor allocation,
+ * which mg_blobset_free frees. */
+typedef struct {
+  uint32_t  n;
+  uint64_t *labels;      /* [n] ascending */
+  uint64_t *offset;      /* [n] into blob */
+  uint64_t *size;        /* [n] */
+  uint32_t *nverts;      /* [n] */
+  uint32_t *ntris;       /* [n] */
+  float    *bbox;        /* [6n] */
+  uint8_t  *blob;
+  uint64_t  blob_bytes;
+} mg_blobset;
 
 /* Label selection folded into one lookup table (replaces the host
  * fastremap sequence of mesh.py:200-204 and 357-369). Every voxel is
@@ -225,6 +269,31 @@ int mg_mesh_chunk_filled(mg_ctx *ctx, const void *labels,
                          const mg_label_map *map,
                          uint32_t fill_level,
                          mg_meshset **out);
+
+/* mg_mesh_chunk_mapped, ending in the encoded fragments instead of the
+ * meshes — replaces MeshTask's per-label host loop (mesh.py:434-448: shift
+ * into global nm, bounding box, precomputed or draco encoding). The
+ * pipeline is the same through the simplifier; the encode stage then writes
+ * every label's bytes and box on the device, byte for byte what the host
+ * loop gives for the meshes mg_mesh_chunk_mapped would return, and only the
+ * blob and the per-label tables are downloaded. MG_FLAG_DEVICE_ONLY runs
+ * the stage and returns an empty set; MG_FLAG_SKIP_H2D keeps its meaning.
+ * There is no fill_holes variant.
+ * Errors besides mg_mesh_chunk_mapped's (non-zero return + mg_last_error,
+ * before any kernel, the ctx stays usable): NULL params, an unknown format,
+ * a non-finite shift / q_origin / q_range, q_range <= 0, q_bits outside
+ * 1..32 (the q_ fields are read for MG_ENC_DRACO only). */
+int mg_mesh_chunk_encoded(mg_ctx *ctx, const void *labels,
+                          int sx, int sy, int sz, int dtype,
+                          float rx, float ry, float rz,
+                          uint32_t reduction_factor, float max_error,
+                          int voxel_centered, uint64_t dust_threshold,
+                          uint32_t flags,
+                          const mg_label_map *map,
+                          const mg_encode_params *params,
+                          mg_blobset **out);
+
+void mg_blobset_free(mg_blobset *bs);
 
 /* Mesh the hole volume left by the last mg_mesh_chunk_filled
  * (fill_level > 0) on this ctx — replaces Mesher.mesh(hole_labels) +

@@ -791,19 +791,11 @@ static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
     int64_t cz = (int64_t)(d % k.dn.nz) + k.dn.lo[2];
     int64_t cy = (int64_t)((d / k.dn.nz) % k.dn.ny) + k.dn.lo[1];
     int64_t cx = (int64_t)(d / k.dn.nz / k.dn.ny) + k.dn.lo[0];
-    mg_mesh &mm = ms->meshes[m];
-    mm.label = ((uint64_t)(cx + (1 << 20)) << 42) |
-               ((uint64_t)(cy + (1 << 20)) << 21) |
-               (uint64_t)(cz + (1 << 20));
-    mm.nverts = vb[o + 1] - vb[o];
-    mm.ntris = fb[o + 1] - fb[o];
-    mm.verts = h_verts + 3ull * vb[o];
-    mm.faces = h_faces + 3ull * fb[o];
-    ms->labels_arr[m] = mm.label;
-    ms->voff_arr[m] = vb[o];
-    ms->nv_arr[m] = mm.nverts;
-    ms->foff_arr[m] = fb[o];
-    ms->nf_arr[m] = mm.ntris;
+    const uint64_t label = ((uint64_t)(cx + (1 << 20)) << 42) |
+                           ((uint64_t)(cy + (1 << 20)) << 21) |
+                           (uint64_t)(cz + (1 << 20));
+    set_mesh(ms, m, label, vb[o], vb[o + 1] - vb[o], fb[o],
+             fb[o + 1] - fb[o]);
     order[m] = m;
   }
   // dict order: cells whose stream starts with an interior face (sort key

@@ -1400,17 +1400,8 @@ static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
   });
   for (uint32_t m = 0; m < nlabels; ++m) {
     uint32_t l = idx[m];
-    mg_mesh &mm = ms->meshes[m];
-    mm.label = h_label_values[l];
-    mm.nverts = h_vbase[l + 1] - h_vbase[l];
-    mm.ntris = h_tri_off[l + 1] - h_tri_off[l];
-    mm.verts = h_verts + 3ull * h_vbase[l];
-    mm.faces = h_faces + 3ull * h_tri_off[l];
-    ms->labels_arr[m] = mm.label;
-    ms->voff_arr[m] = h_vbase[l];
-    ms->nv_arr[m] = mm.nverts;
-    ms->foff_arr[m] = h_tri_off[l];
-    ms->nf_arr[m] = mm.ntris;
+    set_mesh(ms, m, h_label_values[l], h_vbase[l], h_vbase[l + 1] - h_vbase[l],
+             h_tri_off[l], h_tri_off[l + 1] - h_tri_off[l]);
   }
   *out = ms;
   return 0;
@@ -1418,33 +1409,63 @@ static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
 
 #include "encode.hip"
 
-// The call's empty result: a meshset, or a blobset for an encoded call.
-static int empty_result(mg_ctx *c, mg_meshset **out, mg_blobset **bout) {
-  return bout ? new_blobset(c, 0, bout) : new_meshset(c, 0, out);
+// One chunk call as its caller gave it, in the order of the C signatures; the
+// four mg_mesh_chunk* entry points and mg_mesh_holes each fill one. Exactly
+// one destination is set, and which one says how the call ends: `out` in
+// extract_meshset, `bout` (an encoded call, with `ep`) in run_encode.
+struct ChunkRequest {
+  const void *labels;  // host volume; not read under MG_FLAG_SKIP_H2D
+  int sx, sy, sz, dtype;
+  float rx, ry, rz;
+  uint32_t reduction_factor;
+  float max_error;
+  int voxel_centered;
+  uint64_t dust_threshold;
+  uint32_t flags;
+  const mg_label_map *map;     // null: no label map
+  uint32_t fill_level;
+  const mg_encode_params *ep;  // null for a meshset call
+  mg_meshset **out;
+  mg_blobset **bout;
+  EncParams enc;  // ep as check_encode_params accepted it (mesh_chunk_checked)
+};
+
+static int empty_result(mg_ctx *c, const ChunkRequest &r) {
+  return r.bout ? new_blobset(c, 0, r.bout) : new_meshset(c, 0, r.out);
 }
 
-// enc / bout are set together, by mg_mesh_chunk_encoded: the call then ends
-// in run_encode and *bout instead of extract_meshset and *out.
-static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
-                           int sx, int sy, int sz, int dtype,
-                           float rx, float ry, float rz,
-                           uint32_t reduction_factor, float max_error,
-                           int voxel_centered, uint64_t dust_threshold,
-                           uint32_t flags, const mg_label_map *map,
-                           uint32_t fill_level, mg_meshset **out,
-                           const EncParams *enc = nullptr,
-                           mg_blobset **bout = nullptr) {
+// The one writer of c->stats' stage times (ms_labelmap aside: run_label_map
+// syncs for it), once the call's stream is synchronised. meshed = false: no
+// triangles, so the events past the count pass are an earlier call's and
+// their fields stay 0.
+static void write_stage_times(mg_ctx *c, const ChunkRequest &r, bool meshed) {
+  mg_stats &st = c->stats;
+  st.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
+  if (r.fill_level) st.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
+  if (!meshed) return;
+  st.ms_count = ev_ms(c, EV_H2D_END, EV_COUNT_END);
+  st.ms_scan = ev_ms(c, EV_COUNT_END, EV_SCAN_END);
+  st.ms_emit = ev_ms(c, EV_SCAN_END, EV_EMIT_END);
+  st.ms_partition = ev_ms(c, EV_EMIT_END, EV_PARTITION_END);
+  st.ms_weld = ev_ms(c, EV_PARTITION_END, EV_WELD_END);
+  st.ms_simplify = ev_ms(c, EV_WELD_END, EV_SIMPLIFY_END);
+  st.ms_d2h = ev_ms(c, r.bout ? EV_ENCODE_END : EV_SIMPLIFY_END, EV_END);
+  if (r.bout) st.ms_encode = ev_ms(c, EV_SIMPLIFY_END, EV_ENCODE_END);
+  st.ms_total = ev_ms(c, EV_START, EV_END);
+}
+
+static int mesh_chunk_impl(mg_ctx *c, const ChunkRequest &r) {
   ChunkCall k = {};
-  k.sx = sx; k.sy = sy; k.sz = sz; k.dtype = dtype;
-  k.esize = (dtype == MG_U64) ? 8 : 4;
-  k.nvox = (uint64_t)sx * sy * sz;
-  k.rx = rx; k.ry = ry; k.rz = rz;
-  k.voxel_centered = voxel_centered;
+  k.sx = r.sx; k.sy = r.sy; k.sz = r.sz; k.dtype = r.dtype;
+  k.esize = (r.dtype == MG_U64) ? 8 : 4;
+  k.nvox = (uint64_t)r.sx * r.sy * r.sz;
+  k.rx = r.rx; k.ry = r.ry; k.rz = r.rz;
+  k.voxel_centered = r.voxel_centered;
   GridDims &g = k.g;
-  g.sx = sx; g.sy = sy; g.sz = sz;
-  g.ncx = sx > 1 ? sx - 1 : 0;
-  g.ncy = sy > 1 ? sy - 1 : 0;
-  g.ncz = sz > 1 ? sz - 1 : 0;
+  g.sx = r.sx; g.sy = r.sy; g.sz = r.sz;
+  g.ncx = r.sx > 1 ? r.sx - 1 : 0;
+  g.ncy = r.sy > 1 ? r.sy - 1 : 0;
+  g.ncz = r.sz > 1 ? r.sz - 1 : 0;
   g.nsegx = (g.ncx + WAVE - 1) / WAVE;
   g.nseg = g.nsegx * g.ncy * g.ncz;
 
@@ -1452,26 +1473,27 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
   c->stats.bytes_read_algorithmic = k.nvox * k.esize;
   hipStream_t s = c->stream;
 
-  // trivial empty-cell-grid case
+  // trivial empty-cell-grid case: nothing is queued, no stage time
   if (g.nseg == 0) {
-    if (int e = empty_result(c, out, bout)) return e;
-    if (fill_level) set_hole_stash(c, k);  // nothing to mesh there either
+    if (int e = empty_result(c, r)) return e;
+    if (r.fill_level) set_hole_stash(c, k);  // nothing to mesh there either
     return 0;
   }
 
   HIP_TRY(c, hipEventRecord(c->ev[EV_START], s), 10);
-  if (int e = upload_labels(c, k, labels_host, flags)) return e;
+  if (int e = upload_labels(c, k, r.labels, r.flags)) return e;
   HIP_TRY(c, hipEventRecord(c->ev[EV_H2D_END], s), 11);
-  if (dust_threshold > 0)
-    if (int e = run_dust(c, k, dust_threshold)) return e;
-  if (map)
-    if (int e = run_label_map(c, k, map)) return e;
+  if (r.dust_threshold > 0)
+    if (int e = run_dust(c, k, r.dust_threshold)) return e;
+  if (r.map)
+    if (int e = run_label_map(c, k, r.map)) return e;
   // fill_holes on the dusted + mapped labels (mesh.py:211-228): the
   // resident volume becomes the filled one, the hole volume stays in
   // c->holes for mg_mesh_holes
-  if (fill_level) {
+  if (r.fill_level) {
     HIP_TRY(c, hipEventRecord(c->ev[EV_FILL_START], s), 56);
-    if (int e = run_fill_holes(c, dtype, sx, sy, sz, fill_level, nullptr))
+    if (int e = run_fill_holes(c, r.dtype, r.sx, r.sy, r.sz, r.fill_level,
+                               nullptr))
       return e;
     HIP_TRY(c, hipEventRecord(c->ev[EV_FILL_END], s), 56);
     set_hole_stash(c, k);
@@ -1479,39 +1501,25 @@ static int mesh_chunk_impl(mg_ctx *c, const void *labels_host,
 
   if (int e = run_count_emit(c, k)) return e;
   if (k.T == 0 || k.nlabels == 0) {
-    if (int e = empty_result(c, out, bout)) return e;
+    if (int e = empty_result(c, r)) return e;
     HIP_TRY(c, hipStreamSynchronize(s), 14);
-    c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
-    if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
+    write_stage_times(c, r, false);
     return 0;
   }
   if (int e = run_partition(c, k)) return e;
   if (int e = run_weld(c, k)) return e;
   // [6] per-label quadric simplification (mesh.py:376-381 semantics)
-  if (reduction_factor > 1 && k.T > 0)
-    if (int e = run_simplify(c, k.nlabels, k.lab_sorted, reduction_factor,
-                             max_error, &k.T, &k.V))
+  if (r.reduction_factor > 1 && k.T > 0)
+    if (int e = run_simplify(c, k.nlabels, k.lab_sorted, r.reduction_factor,
+                             r.max_error, &k.T, &k.V))
       return e;
   HIP_TRY(c, hipEventRecord(c->ev[EV_SIMPLIFY_END], s), 22);
-  if (enc) {
-    if (int e = run_encode(c, k, flags, *enc, bout)) return e;
-  } else {
-    if (int e = extract_meshset(c, k, flags, out)) return e;
-  }
+  if (int e = r.bout ? run_encode(c, k, r.flags, r.enc, r.bout)
+                     : extract_meshset(c, k, r.flags, r.out))
+    return e;
   HIP_TRY(c, hipEventRecord(c->ev[EV_END], s), 25);
   HIP_TRY(c, hipStreamSynchronize(s), 25);
-
-  c->stats.ms_h2d = ev_ms(c, EV_START, EV_H2D_END);
-  c->stats.ms_count = ev_ms(c, EV_H2D_END, EV_COUNT_END);
-  c->stats.ms_scan = ev_ms(c, EV_COUNT_END, EV_SCAN_END);
-  c->stats.ms_emit = ev_ms(c, EV_SCAN_END, EV_EMIT_END);
-  c->stats.ms_partition = ev_ms(c, EV_EMIT_END, EV_PARTITION_END);
-  c->stats.ms_weld = ev_ms(c, EV_PARTITION_END, EV_WELD_END);
-  c->stats.ms_simplify = ev_ms(c, EV_WELD_END, EV_SIMPLIFY_END);
-  c->stats.ms_d2h = ev_ms(c, enc ? EV_ENCODE_END : EV_SIMPLIFY_END, EV_END);
-  if (enc) c->stats.ms_encode = ev_ms(c, EV_SIMPLIFY_END, EV_ENCODE_END);
-  c->stats.ms_total = ev_ms(c, EV_START, EV_END);
-  if (fill_level) c->stats.ms_fill = ev_ms(c, EV_FILL_START, EV_FILL_END);
+  write_stage_times(c, r, true);
   return 0;
 }
 
@@ -1571,45 +1579,35 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
 
 #include "chunk_mesh.hip"
 
-// mg_mesh_chunk_filled and mg_mesh_chunk_encoded: argument checks, then
-// mesh_chunk_impl. ep / bout belong to the encoded call (encoded = true).
-static int mesh_chunk_checked(mg_ctx *c, const void *labels, int sx, int sy,
-                              int sz, int dtype, float rx, float ry, float rz,
-                              uint32_t reduction_factor, float max_error,
-                              int voxel_centered, uint64_t dust_threshold,
-                              uint32_t flags, const mg_label_map *map,
-                              uint32_t fill_level, mg_meshset **out,
-                              bool encoded, const mg_encode_params *ep,
-                              mg_blobset **bout) {
+// The argument checks of the four mg_mesh_chunk* calls, in the order their
+// return codes document (the earlier check wins), then mesh_chunk_impl.
+static int mesh_chunk_checked(mg_ctx *c, ChunkRequest r) {
   if (!c) { SET_ERR(c, "null ctx"); return 1; }
   std::lock_guard<std::mutex> g(c->lock);
   c->err.clear();
-  if (fill_level > 2) {
+  if (r.fill_level > 2) {
     SET_ERR(c, "fill_level %u: only levels 0-2 are implemented (level 3 "
-            "needs a multilabel dilation, 4+ a merge threshold)", fill_level);
+            "needs a multilabel dilation, 4+ a merge threshold)",
+            r.fill_level);
     return 6;
   }
-  if (fill_level && (flags & MG_FLAG_SKIP_H2D)) {
+  if (r.fill_level && (r.flags & MG_FLAG_SKIP_H2D)) {
     SET_ERR(c, "fill_holes cannot be combined with MG_FLAG_SKIP_H2D (the "
             "resident volume is already filled)");
     return 6;
   }
-  if (!labels || (encoded ? !bout : !out)) {
+  if (!r.labels || (!r.out && !r.bout)) {
     SET_ERR(c, "null argument");
     return 1;
   }
-  EncParams enc;
-  if (encoded)
-    if (int e = check_encode_params(c, ep, &enc)) return e;
+  if (r.bout)
+    if (int e = check_encode_params(c, r.ep, &r.enc)) return e;
   c->holes_valid = false;  // a stash belongs to the call just before
-  if (int e = check_volume_args(c, sx, sy, sz, dtype)) return e;
-  if (map)
-    if (int e = check_label_map(c, map, dtype, flags)) return e;
+  if (int e = check_volume_args(c, r.sx, r.sy, r.sz, r.dtype)) return e;
+  if (r.map)
+    if (int e = check_label_map(c, r.map, r.dtype, r.flags)) return e;
   HIP_TRY(c, hipSetDevice(c->device), 4);
-  return mesh_chunk_impl(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                         reduction_factor, max_error, voxel_centered,
-                         dust_threshold, flags, map, fill_level, out,
-                         encoded ? &enc : nullptr, encoded ? bout : nullptr);
+  return mesh_chunk_impl(c, r);
 }
 
 extern "C" {
@@ -1620,10 +1618,10 @@ int mg_mesh_chunk_filled(mg_ctx *c, const void *labels, int sx, int sy,
                          int voxel_centered, uint64_t dust_threshold,
                          uint32_t flags, const mg_label_map *map,
                          uint32_t fill_level, mg_meshset **out) {
-  return mesh_chunk_checked(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                            reduction_factor, max_error, voxel_centered,
-                            dust_threshold, flags, map, fill_level, out,
-                            false, nullptr, nullptr);
+  return mesh_chunk_checked(
+      c, {labels, sx, sy, sz, dtype, rx, ry, rz, reduction_factor, max_error,
+          voxel_centered, dust_threshold, flags, map, fill_level, nullptr,
+          out, nullptr});
 }
 
 int mg_mesh_chunk_encoded(mg_ctx *c, const void *labels, int sx, int sy,
@@ -1632,10 +1630,10 @@ int mg_mesh_chunk_encoded(mg_ctx *c, const void *labels, int sx, int sy,
                           int voxel_centered, uint64_t dust_threshold,
                           uint32_t flags, const mg_label_map *map,
                           const mg_encode_params *params, mg_blobset **out) {
-  return mesh_chunk_checked(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                            reduction_factor, max_error, voxel_centered,
-                            dust_threshold, flags, map, 0u, nullptr, true,
-                            params, out);
+  return mesh_chunk_checked(
+      c, {labels, sx, sy, sz, dtype, rx, ry, rz, reduction_factor, max_error,
+          voxel_centered, dust_threshold, flags, map, 0u, params, nullptr,
+          out});
 }
 
 // the blob is ctx-owned (pinned, reused); this frees the descriptor
@@ -1647,9 +1645,10 @@ int mg_mesh_chunk_mapped(mg_ctx *c, const void *labels, int sx, int sy,
                          int voxel_centered, uint64_t dust_threshold,
                          uint32_t flags, const mg_label_map *map,
                          mg_meshset **out) {
-  return mg_mesh_chunk_filled(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                              reduction_factor, max_error, voxel_centered,
-                              dust_threshold, flags, map, 0u, out);
+  return mesh_chunk_checked(
+      c, {labels, sx, sy, sz, dtype, rx, ry, rz, reduction_factor, max_error,
+          voxel_centered, dust_threshold, flags, map, 0u, nullptr, out,
+          nullptr});
 }
 
 int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
@@ -1657,9 +1656,10 @@ int mg_mesh_chunk(mg_ctx *c, const void *labels, int sx, int sy, int sz,
                   uint32_t reduction_factor, float max_error,
                   int voxel_centered, uint64_t dust_threshold,
                   uint32_t flags, mg_meshset **out) {
-  return mg_mesh_chunk_mapped(c, labels, sx, sy, sz, dtype, rx, ry, rz,
-                              reduction_factor, max_error, voxel_centered,
-                              dust_threshold, flags, nullptr, out);
+  return mesh_chunk_checked(
+      c, {labels, sx, sy, sz, dtype, rx, ry, rz, reduction_factor, max_error,
+          voxel_centered, dust_threshold, flags, nullptr, 0u, nullptr, out,
+          nullptr});
 }
 
 int mg_mesh_holes(mg_ctx *c, float rx, float ry, float rz,
@@ -1679,11 +1679,11 @@ int mg_mesh_holes(mg_ctx *c, float rx, float ry, float rz,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   // the hole volume becomes the resident label volume: no upload
   std::swap(c->labels, c->holes);
-  return mesh_chunk_impl(c, nullptr, c->holes_sx, c->holes_sy, c->holes_sz,
-                         c->holes_dtype, rx, ry, rz, reduction_factor,
-                         max_error, voxel_centered, 0,
-                         (flags & MG_FLAG_DEVICE_ONLY) | MG_FLAG_SKIP_H2D,
-                         nullptr, 0u, out);
+  return mesh_chunk_impl(
+      c, {nullptr, c->holes_sx, c->holes_sy, c->holes_sz, c->holes_dtype, rx,
+          ry, rz, reduction_factor, max_error, voxel_centered, 0,
+          (flags & MG_FLAG_DEVICE_ONLY) | MG_FLAG_SKIP_H2D, nullptr, 0u,
+          nullptr, out, nullptr});
 }
 
 int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,

@@ -352,3 +352,16 @@ static mg_meshset *alloc_meshset(uint32_t n, uint32_t extra_u32_per_mesh) {
   ms->nf_arr = ms->foff_arr + n;
   return ms;
 }
+
+// Entry m of a meshset whose verts_base / faces_base are set: mesh `label`
+// is nv vertices from vertex voff and nf triangles from triangle foff.
+static void set_mesh(mg_meshset *ms, uint32_t m, uint64_t label,
+                     uint32_t voff, uint32_t nv, uint32_t foff, uint32_t nf) {
+  ms->meshes[m] = {label, nv, nf, ms->verts_base + 3ull * voff,
+                   ms->faces_base + 3ull * foff};
+  ms->labels_arr[m] = label;
+  ms->voff_arr[m] = voff;
+  ms->nv_arr[m] = nv;
+  ms->foff_arr[m] = foff;
+  ms->nf_arr[m] = nf;
+}

@@ -229,6 +229,27 @@ def _draco_numbers(draco):
     return [float(x) for x in origin], rng, bits
 
 
+# The arguments every mg_mesh_chunk* function starts with (ctx, labels,
+# sx, sy, sz, dtype, rx, ry, rz, reduction_factor, max_error,
+# voxel_centered, dust_threshold, flags: Engine._chunk_args builds them) ...
+_CHUNK_ARGTYPES = [
+    ctypes.c_void_p, ctypes.c_void_p,
+    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+    ctypes.c_float, ctypes.c_float, ctypes.c_float,
+    ctypes.c_uint32, ctypes.c_float, ctypes.c_int,
+    ctypes.c_uint64, ctypes.c_uint32,
+]
+# ... and what each of the four adds behind them
+_P_MAP = ctypes.POINTER(_MgLabelMap)
+_PP_MESHSET = ctypes.POINTER(ctypes.POINTER(_MgMeshSet))
+_CHUNK_TAIL_ARGTYPES = {
+    "mg_mesh_chunk": [_PP_MESHSET],
+    "mg_mesh_chunk_mapped": [_P_MAP, _PP_MESHSET],
+    "mg_mesh_chunk_filled": [_P_MAP, ctypes.c_uint32, _PP_MESHSET],
+    "mg_mesh_chunk_encoded": [_P_MAP, ctypes.POINTER(_MgEncodeParams),
+                              ctypes.POINTER(ctypes.POINTER(_MgBlobSet))],
+}
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -251,30 +272,10 @@ def load_library() -> ctypes.CDLL:
         lib.mg_init.restype = ctypes.c_void_p
         lib.mg_init.argtypes = [ctypes.c_int]
         lib.mg_destroy.argtypes = [ctypes.c_void_p]
-        lib.mg_mesh_chunk.restype = ctypes.c_int
-        lib.mg_mesh_chunk.argtypes = [
-            ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-            ctypes.c_float, ctypes.c_float, ctypes.c_float,
-            ctypes.c_uint32, ctypes.c_float, ctypes.c_int,
-            ctypes.c_uint64, ctypes.c_uint32,
-            ctypes.POINTER(ctypes.POINTER(_MgMeshSet)),
-        ]
-        lib.mg_mesh_chunk_mapped.restype = ctypes.c_int
-        lib.mg_mesh_chunk_mapped.argtypes = (
-            lib.mg_mesh_chunk.argtypes[:-1]
-            + [ctypes.POINTER(_MgLabelMap)]
-            + lib.mg_mesh_chunk.argtypes[-1:])
-        lib.mg_mesh_chunk_filled.restype = ctypes.c_int
-        lib.mg_mesh_chunk_filled.argtypes = (
-            lib.mg_mesh_chunk.argtypes[:-1]
-            + [ctypes.POINTER(_MgLabelMap), ctypes.c_uint32]
-            + lib.mg_mesh_chunk.argtypes[-1:])
-        lib.mg_mesh_chunk_encoded.restype = ctypes.c_int
-        lib.mg_mesh_chunk_encoded.argtypes = (
-            lib.mg_mesh_chunk.argtypes[:-1]
-            + [ctypes.POINTER(_MgLabelMap), ctypes.POINTER(_MgEncodeParams),
-               ctypes.POINTER(ctypes.POINTER(_MgBlobSet))])
+        for name, tail in _CHUNK_TAIL_ARGTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = _CHUNK_ARGTYPES + tail
         lib.mg_blobset_free.argtypes = [ctypes.POINTER(_MgBlobSet)]
         lib.mg_mesh_holes.restype = ctypes.c_int
         lib.mg_mesh_holes.argtypes = [
@@ -331,10 +332,23 @@ def _mg_dtype(arr: np.ndarray) -> int:
     raise ValueError(f"unsupported label dtype {arr.dtype}")
 
 
-def _default_device() -> int:
-    """Device of the module-level calls: MESHGINE_DEVICE, else LOCAL_RANK."""
-    return int(os.environ.get("MESHGINE_DEVICE",
-                              os.environ.get("LOCAL_RANK", "0")))
+def _np_array(ptr, n: int, width=None, copy: bool = False) -> np.ndarray:
+    """n elements (n rows of `width`) behind a typed ctypes pointer as a
+    numpy array: a view of that memory, or a copy. n == 0 never reads ptr."""
+    shape = (n,) if width is None else (n, width)
+    if not n:
+        return np.zeros(shape, dtype=ptr._type_)
+    arr = np.ctypeslib.as_array(ptr, shape=shape)
+    return arr.copy() if copy else arr
+
+
+def _engine(device_id: Optional[int]) -> "Engine":
+    """The shared Engine of the module-level calls: on device_id, else on
+    MESHGINE_DEVICE, else on LOCAL_RANK."""
+    if device_id is None:
+        device_id = int(os.environ.get("MESHGINE_DEVICE",
+                                       os.environ.get("LOCAL_RANK", "0")))
+    return Engine.get(device_id)
 
 
 def _fill_level_unsupported(what: str) -> NotImplementedError:
@@ -429,6 +443,37 @@ class Engine:
                 "resident volume has already been filled")
         if fill_holes:
             copy = True
+        args, cmap, _keep = self._chunk_args(
+            labels, resolution, reduction_factor, max_error, voxel_centered,
+            dust_threshold, device_only, skip_h2d, label_map)
+        # the narrowest entry point that takes what was asked for
+        if fill_holes:
+            fn, tail = "mg_mesh_chunk_filled", (cmap, fill_holes)
+        elif cmap is not None:
+            fn, tail = "mg_mesh_chunk_mapped", (cmap,)
+        else:
+            fn, tail = "mg_mesh_chunk", ()
+        with self._lock:
+            out = ctypes.POINTER(_MgMeshSet)()
+            rc = getattr(self.lib, fn)(*args, *tail, ctypes.byref(out))
+            self._check(rc, fn)
+            result = self._collect(out, copy)
+            if not fill_holes:
+                return result
+            self.last_fill_stats = self.stats()
+            out = ctypes.POINTER(_MgMeshSet)()
+            rc = self.lib.mg_mesh_holes(  # resolution .. voxel_centered, flags
+                self.ctx, *args[6:12],
+                MG_FLAG_DEVICE_ONLY if device_only else 0, ctypes.byref(out))
+            self._check(rc, "mg_mesh_holes")
+            return result, self._collect(out, True)
+
+    def _chunk_args(self, labels, resolution, reduction_factor, max_error,
+                    voxel_centered, dust_threshold, device_only, skip_h2d,
+                    label_map):
+        """The one marshalling of a chunk call: (the _CHUNK_ARGTYPES
+        arguments, a reference to the mg_label_map or None, the arrays the
+        two point into — the caller holds them until the call returns)."""
         labels = np.asfortranarray(labels)
         dtype = _mg_dtype(labels)
         sx, sy, sz = labels.shape
@@ -440,38 +485,8 @@ class Engine:
             float(resolution[0]), float(resolution[1]), float(resolution[2]),
             int(reduction_factor), float(max_error),
             int(bool(voxel_centered)), int(dust_threshold), flags)
-        cmap, _keep = self._label_map_struct(label_map, skip_h2d)
-        with self._lock:
-            out = ctypes.POINTER(_MgMeshSet)()
-            if fill_holes:
-                fn = "mg_mesh_chunk_filled"
-                rc = self.lib.mg_mesh_chunk_filled(
-                    *args, ctypes.byref(cmap) if cmap is not None else None,
-                    fill_holes, ctypes.byref(out))
-            elif cmap is None:
-                fn = "mg_mesh_chunk"
-                rc = self.lib.mg_mesh_chunk(*args, ctypes.byref(out))
-            else:
-                fn = "mg_mesh_chunk_mapped"
-                rc = self.lib.mg_mesh_chunk_mapped(
-                    *args, ctypes.byref(cmap), ctypes.byref(out))
-            self._check(rc, fn)
-            result = self._collect(out, copy)
-            if not fill_holes:
-                return result
-            self.last_fill_stats = self.stats()
-            out = ctypes.POINTER(_MgMeshSet)()
-            rc = self.lib.mg_mesh_holes(
-                self.ctx, *args[6:12], flags & MG_FLAG_DEVICE_ONLY,
-                ctypes.byref(out))
-            self._check(rc, "mg_mesh_holes")
-            return result, self._collect(out, True)
-
-    @staticmethod
-    def _label_map_struct(label_map, skip_h2d: bool):
-        """(mg_label_map or None, the arrays it points into)."""
         if label_map is None:
-            return None, None
+            return args, None, (labels,)
         if skip_h2d:
             raise ValueError(
                 "label_map cannot be combined with skip_h2d: the "
@@ -488,7 +503,7 @@ class Engine:
         cmap = _MgLabelMap(
             keys.ctypes.data, vals.ctypes.data, keys.shape[0],
             MG_MAP_MISS_ZERO if miss == 'zero' else MG_MAP_MISS_KEEP)
-        return cmap, (keys, vals)
+        return args, ctypes.byref(cmap), (labels, keys, vals, cmap)
 
     def mesh_chunk_encoded(self, labels: np.ndarray,
                            resolution=(1.0, 1.0, 1.0),
@@ -531,46 +546,22 @@ class Engine:
             if not 0 <= bits < (1 << 32):
                 raise ValueError(f"draco: quantization_bits {bits}")
             params.q_bits = bits
-        labels = np.asfortranarray(labels)
-        dtype = _mg_dtype(labels)
-        sx, sy, sz = labels.shape
-        flags = (MG_FLAG_DEVICE_ONLY if device_only else 0) | \
-                (MG_FLAG_SKIP_H2D if skip_h2d else 0)
-        cmap, _keep = self._label_map_struct(label_map, skip_h2d)
+        args, cmap, _keep = self._chunk_args(
+            labels, resolution, reduction_factor, max_error, voxel_centered,
+            dust_threshold, device_only, skip_h2d, label_map)
         with self._lock:
             out = ctypes.POINTER(_MgBlobSet)()
             rc = self.lib.mg_mesh_chunk_encoded(
-                self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
-                sx, sy, sz, dtype,
-                float(resolution[0]), float(resolution[1]),
-                float(resolution[2]),
-                int(reduction_factor), float(max_error),
-                int(bool(voxel_centered)), int(dust_threshold), flags,
-                ctypes.byref(cmap) if cmap is not None else None,
-                ctypes.byref(params), ctypes.byref(out))
+                *args, cmap, ctypes.byref(params), ctypes.byref(out))
             self._check(rc, "mg_mesh_chunk_encoded")
             try:
                 bs = out.contents
                 n = int(bs.n)
-                nb = int(bs.blob_bytes)
-
-                def table(ptr, width=None):
-                    if not n:
-                        return np.zeros((0,) if width is None else (0, width),
-                                        dtype=ptr._type_)
-                    shape = (n,) if width is None else (n, width)
-                    return np.ctypeslib.as_array(ptr, shape=shape).copy()
-
-                if nb:
-                    blob = np.ctypeslib.as_array(bs.blob, shape=(nb,))
-                    if copy:
-                        blob = blob.copy()
-                else:
-                    blob = np.zeros(0, dtype=np.uint8)
                 return EncodedChunk(
-                    table(bs.labels), table(bs.offset), table(bs.size),
-                    table(bs.nverts), table(bs.ntris), table(bs.bbox, 6),
-                    blob)
+                    *(_np_array(p, n, copy=True) for p in (
+                        bs.labels, bs.offset, bs.size, bs.nverts, bs.ntris)),
+                    _np_array(bs.bbox, n, 6, copy=True),
+                    _np_array(bs.blob, int(bs.blob_bytes), copy=copy))
             finally:
                 self.lib.mg_blobset_free(out)
 
@@ -599,20 +590,12 @@ class Engine:
                         ms.verts_base, shape=(max(tv, 1), 3))[:tv]
                     all_f = np.ctypeslib.as_array(
                         ms.faces_base, shape=(max(tt, 1), 3))[:tt]
-                labels = np.ctypeslib.as_array(
-                    ms.labels_arr, shape=(n,)).tolist()
-                voff = np.ctypeslib.as_array(
-                    ms.voff_arr, shape=(n,)).tolist()
-                nv = np.ctypeslib.as_array(
-                    ms.nv_arr, shape=(n,)).tolist()
-                foff = np.ctypeslib.as_array(
-                    ms.foff_arr, shape=(n,)).tolist()
-                nf = np.ctypeslib.as_array(
-                    ms.nf_arr, shape=(n,)).tolist()
+                tables = (_np_array(p, n).tolist() for p in (
+                    ms.labels_arr, ms.voff_arr, ms.nv_arr, ms.foff_arr,
+                    ms.nf_arr))
                 result = {
                     lab: (all_v[vo:vo + kv], all_f[fo:fo + kf])
-                    for lab, vo, kv, fo, kf
-                    in zip(labels, voff, nv, foff, nf)
+                    for lab, vo, kv, fo, kf in zip(*tables)
                 }
         finally:
             self.lib.mg_meshset_free(out)
@@ -668,8 +651,8 @@ class Engine:
                 ctypes.byref(ov), ctypes.byref(onv),
                 ctypes.byref(of), ctypes.byref(ont))
             self._check(rc, "mg_simplify_mesh")
-            out_v = np.ctypeslib.as_array(ov, shape=(onv.value, 3)).copy()
-            out_f = np.ctypeslib.as_array(of, shape=(ont.value, 3)).copy()
+            out_v = _np_array(ov, onv.value, 3, copy=True)
+            out_f = _np_array(of, ont.value, 3, copy=True)
         return out_v, out_f
 
     def chunk_mesh(self, verts: np.ndarray, faces: np.ndarray,
@@ -696,8 +679,7 @@ class Engine:
             self._check(rc, "mg_chunk_mesh")
             n = int(out.contents.nmeshes)
             # read out_order before _collect frees the descriptor
-            idx = np.ctypeslib.as_array(order, shape=(n,)).tolist() \
-                if n else []
+            idx = _np_array(order, n).tolist()
             by_label = self._collect(out, True)
         labels = list(by_label)  # ascending label = meshes[] order
         mask = (1 << 21) - 1
@@ -725,9 +707,7 @@ def mesh_chunk(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                copy: bool = True, label_map=None, fill_holes: int = 0):
     """Module-level product mesher (the default MeshTask path). With
     fill_holes=1|2 returns the pair (filled_meshes, hole_meshes)."""
-    if device_id is None:
-        device_id = _default_device()
-    return Engine.get(device_id).mesh_chunk(
+    return _engine(device_id).mesh_chunk(
         labels, resolution, reduction_factor, max_error, voxel_centered,
         dust_threshold=dust_threshold, copy=copy, label_map=label_map,
         fill_holes=fill_holes)
@@ -753,9 +733,7 @@ def mesh_chunk_encoded(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                        shift=(0.0, 0.0, 0.0), encoding: str = 'precomputed',
                        draco=None, copy: bool = True) -> EncodedChunk:
     """Module-level encoded mesher: see Engine.mesh_chunk_encoded."""
-    if device_id is None:
-        device_id = _default_device()
-    return Engine.get(device_id).mesh_chunk_encoded(
+    return _engine(device_id).mesh_chunk_encoded(
         labels, resolution, reduction_factor, max_error, voxel_centered,
         dust_threshold=dust_threshold, label_map=label_map, shift=shift,
         encoding=encoding, draco=draco, copy=copy)
@@ -779,18 +757,14 @@ def fill_holes(labels: np.ndarray, level: int = 1,
                device_id: Optional[int] = None):
     """Module-level hole filling -> (filled, holes, rounds); see
     Engine.fill_holes."""
-    if device_id is None:
-        device_id = _default_device()
-    return Engine.get(device_id).fill_holes(labels, level)
+    return _engine(device_id).fill_holes(labels, level)
 
 
 def chunk_mesh(mesh, scale, offset, device_id: Optional[int] = None):
     """Module-level grid chunker (the default multires path): Mesh ->
     {(cx, cy, cz): Mesh}, the shape and order of meshops.chunk_mesh."""
     from .meshes import Mesh
-    if device_id is None:
-        device_id = _default_device()
-    cells = Engine.get(device_id).chunk_mesh(
+    cells = _engine(device_id).chunk_mesh(
         mesh.vertices, mesh.faces, scale, offset)
     return {key: Mesh(v, f, id=mesh.id) for key, (v, f) in cells.items()}
 
@@ -805,8 +779,6 @@ def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,
     if nt <= target:
         return Mesh(mesh.vertices.copy(), mesh.faces.copy(), id=mesh.id)
     rf = max(nt // target, 2)
-    if device_id is None:
-        device_id = _default_device()
-    v, f = Engine.get(device_id).simplify_mesh(
+    v, f = _engine(device_id).simplify_mesh(
         mesh.vertices, mesh.faces, rf, max_error)
     return Mesh(v, f, id=mesh.id)

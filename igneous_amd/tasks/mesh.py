@@ -1,6 +1,6 @@
 """MeshTask — drop-in for igneous.tasks.MeshTask, MI355X-native compute.
 
-Mirrors the reference class at /root/reference/igneous/tasks/mesh/mesh.py:
+Mirrors the reference class (igneous/tasks/mesh/mesh.py, "mesh.py" below):
   - ctor signature (shape, offset, layer_path, **kwargs) and the full
     options dict of mesh.py:98-129 (kwargs surface preserved verbatim);
   - execute() flow of mesh.py:140-265: clamp bounds, pad by
@@ -13,19 +13,19 @@ Mirrors the reference class at /root/reference/igneous/tasks/mesh/mesh.py:
     manifests (mesh.py:419-430) and spatial index (mesh.py:452-464).
 
 The compute crosses to the GPU exactly where the reference crosses into
-zmesh C++ (mesh.py:245 and mesh.py:374-381): one mg_mesh_chunk call on the
-HIP engine produces all labels' welded (and optionally simplified) meshes.
-dust_threshold and the label selection (remap_table / object_ids /
-exclude_object_ids, folded by remap.fold_label_ops) ride the same call as
-device volume passes when the mesher advertises handles_dust /
-handles_label_map. fill_holes levels 1-2 (mesh.py:211-243) ride it too when
-the mesher advertises handles_fill_holes: the fill runs on the device after
-dust and the label selection, the call returns the filled volume's meshes
-and the hole volume's meshes, and the two are concatenated per segment id.
-The per-label loop after the mesher (shift, box, encode — encode_fragment
-below) rides the call as well when the mesher advertises encode_chunk for
-the task's encoding: the engine returns every label's finished bytes and
-box (mg_mesh_chunk_encoded) and the task only uploads them.
+zmesh C++ (mesh.py:245 and mesh.py:374-381). execute() fetches the mesher
+once, reads what it advertises (set_mesher states the protocol) and calls it
+once: the HIP engine's mg_mesh_chunk gives all labels' welded (and optionally
+simplified) meshes. When advertised, the same call carries, as device passes:
+  - handles_dust / handles_label_map: dust_threshold and the label selection
+    (remap_table / object_ids / exclude_object_ids, folded by
+    remap.fold_label_ops) — _select_labels decides host or device;
+  - handles_fill_holes: fill_holes levels 1-2 (mesh.py:211-243) after dust
+    and the selection; the filled and the hole volume's meshes come back
+    and are concatenated per segment id;
+  - encode_chunk, for the task's encoding: the per-label loop after the
+    mesher (shift, box, encode — encode_fragment below); the engine returns
+    finished bytes and boxes (mg_mesh_chunk_encoded), the task uploads them.
 There is no CPU fallback; a missing engine raises.
 
 Deliberate deviations (documented in DESIGN.md):
@@ -60,7 +60,19 @@ _mesher_fn = None
 
 
 def set_mesher(fn) -> None:
-    """Test seam. Pass None to restore the HIP product engine."""
+    """Test seam. Pass None to restore the HIP product engine.
+
+    The protocol: execute() calls fn(data, resolution=, reduction_factor=,
+    max_error=, voxel_centered=, copy=) ONCE and takes its {label: (verts,
+    faces)}. fn accepts `copy` (False: the result may alias storage that
+    lives until fn's next call) and every keyword it advertises by
+    attribute: handles_dust -> dust_threshold=, handles_label_map ->
+    label_map=(keys, vals, miss), handles_fill_holes -> fill_holes= (the
+    result is then the pair (filled, holes)), encode_chunk -> a second
+    callable taking the same keywords plus shift= / encoding= / draco= and
+    returning an engine.EncodedChunk, for the encodings its `formats` lists
+    (all, if it has none). What fn raises, TypeError included, reaches
+    execute()'s caller: there is no second call."""
     global _mesher_fn
     _mesher_fn = fn
 
@@ -70,6 +82,17 @@ def _get_mesher():
         return _mesher_fn
     from .. import engine
     return engine.mesh_chunk
+
+
+class _Capabilities:
+    """What a mesher advertises (set_mesher's protocol), read here only."""
+
+    def __init__(self, mesher):
+        self.dust = getattr(mesher, 'handles_dust', False)
+        self.label_map = getattr(mesher, 'handles_label_map', False)
+        self.fill_holes = getattr(mesher, 'handles_fill_holes', False)
+        self.encode_chunk = getattr(mesher, 'encode_chunk', None)
+        self.formats = getattr(self.encode_chunk, 'formats', None)
 
 
 def encode_fragment(mesh: Mesh, shift, encoding: str, draco_settings=None):
@@ -160,6 +183,8 @@ class MeshTask(RegisteredTask):
     # ------------------------------------------------------------------
     def execute(self):
         opts = self.options
+        mesher = _get_mesher()
+        can = _Capabilities(mesher)
         fill_level = int(opts['fill_holes'] or 0)
         if fill_level >= 3:
             raise NotImplementedError(
@@ -167,19 +192,66 @@ class MeshTask(RegisteredTask):
                 "fastmorph's multilabel dilation and levels >= 4 its "
                 "merge_threshold, whose tie rules cannot be restated "
                 "without the fastmorph source (DESIGN.md §7)")
-        if fill_level > 0 and not getattr(
-                _get_mesher(), 'handles_fill_holes', False):
+        if fill_level > 0 and not can.fill_holes:
             raise NotImplementedError(
                 "fill_holes>0 needs a mesher that fills holes itself "
                 "(handles_fill_holes): the HIP engine does, the injected "
                 "mesher does not")
 
+        data, left_offset = self._download()
+        if data is None:
+            return
+        data, call_kw = self._select_labels(data, can)
+        # the keywords every mesher call carries (set_mesher's protocol)
+        call_kw.update(
+            resolution=tuple(float(r) for r in self._volume.resolution),
+            reduction_factor=int(opts['simplification_factor'] or 0),
+            max_error=float(opts['max_simplification_error']),
+            voxel_centered=True)
+
+        # A mesher that advertises encode_chunk returns every label's
+        # finished bytes and box from one call (the engine's device encode
+        # stage) — no Mesh per label, no host loop. Not with fill_holes
+        # (filled and hole meshes are concatenated on the host) nor under
+        # dry_run (the caller wants the meshes).
+        if (can.encode_chunk is not None and fill_level == 0
+                and not opts['dry_run']
+                and (can.formats is None or opts['encoding'] in can.formats)):
+            encoded = self._encode_on_device(
+                can.encode_chunk, data, call_kw, left_offset)
+            if encoded is not None:
+                del data
+                self._upload(*encoded)
+                return
+
+        if fill_level:
+            # after dust and the label selection, host or device
+            # (mesh.py:193-228); the mesher returns (filled, holes)
+            call_kw['fill_holes'] = fill_level
+        # copy=False: this task consumes (shifts, encodes, uploads) every
+        # mesh before its next engine call, so zero-copy views into the
+        # engine's staging buffers are safe — EXCEPT under dry_run, where
+        # the meshes are handed back to the caller and must own their
+        # storage (the reference returns owned arrays).
+        raw = mesher(data, copy=bool(opts['dry_run']), **call_kw)
+        del data
+        meshes, binaries, bounding_boxes = self._host_loop(
+            raw, fill_level, left_offset)
+        if opts['dry_run']:
+            return (meshes, bounding_boxes)
+        self._upload(binaries, bounding_boxes)
+
+    def _download(self):
+        """Clamp and pad the task's bounds, download, close the dataset's
+        edges. -> (data, left_offset); (None, None) for an all-zero chunk,
+        whose (empty) spatial index is written here."""
+        opts = self.options
         self._volume = PrecomputedVolume(
             self.layer_path, opts['mip'], bounded=False,
             parallel=opts['parallel_download'],
             fill_missing=opts['fill_missing'])
-        self._bounds = Bbox(self.offset, self.shape + self.offset)
-        self._bounds = Bbox.clamp(self._bounds, self._volume.bounds)
+        self._bounds = Bbox.clamp(
+            Bbox(self.offset, self.shape + self.offset), self._volume.bounds)
 
         # 1vx overlap for seam-free stitching between adjacent tasks
         data_bounds = self._bounds.clone()
@@ -187,7 +259,6 @@ class MeshTask(RegisteredTask):
         data_bounds.maxpt += opts['high_padding']
 
         self._mesh_dir = self.get_mesh_dir()
-
         if opts['encoding'] == 'draco':
             from .draco import draco_encoding_settings
             self.draco_encoding_settings = draco_encoding_settings(
@@ -201,32 +272,30 @@ class MeshTask(RegisteredTask):
             )
 
         data = self._volume.download(data_bounds)
-
         if not np.any(data):
             if opts['spatial_index']:
                 self._upload_spatial_index(self._bounds, {})
-            return
-
-        left_offset = Vec(0, 0, 0)
+            return None, None
         if opts['closed_dataset_edges']:
-            data, left_offset = self._handle_dataset_boundary(data, data_bounds)
+            return self._handle_dataset_boundary(data, data_bounds)
+        return data, Vec(0, 0, 0)
 
-        # dust removal: delegated to the engine's device passes when the
-        # mesher advertises support (three HIP volume passes instead of
-        # a multi-second host unique/mask at 512^3); host fallback keeps
-        # the reference semantics for injected CPU meshers
-        mesher_probe = _get_mesher()
-
-        # label selection (remap_table / object_ids / exclude_object_ids):
-        # folded into ONE lookup table and applied by the engine in a
-        # device volume pass when the mesher advertises support; injected
-        # meshers — and folds above the engine's table cap — keep the
-        # host mask_except/remap/mask sequence
+    def _select_labels(self, data, can):
+        """Dust removal and the label selection (remap_table / object_ids /
+        exclude_object_ids), each on the device when the mesher can and on
+        the host otherwise. -> (3-D data, the dust_threshold / label_map
+        keywords that hand the device its share)."""
+        opts = self.options
         if opts['remap_table'] is not None:
             opts['remap_table'] = {
                 int(k): int(v) for k, v in opts['remap_table'].items()}
+
+        # the selection folded into ONE lookup table, applied by the engine
+        # in a device volume pass; meshers that do not advertise it — and
+        # folds above the engine's table cap — keep the host
+        # mask_except/remap/mask sequence
         label_map = None
-        if getattr(mesher_probe, 'handles_label_map', False):
+        if can.label_map:
             label_map = fastremap_np.fold_label_ops(
                 opts['remap_table'], opts['object_ids'],
                 opts['exclude_object_ids'], data.dtype)
@@ -235,105 +304,54 @@ class MeshTask(RegisteredTask):
                 if len(label_map[0]) > LABEL_MAP_MAX_ENTRIES:
                     label_map = None
 
-        device_dust = 0
+        call_kw = {}
         if (opts['dust_threshold'] and not opts['dust_global']
                 and (opts['remap_table'] is None or label_map is not None)
-                and getattr(mesher_probe, 'handles_dust', False)):
-            # a HOST remap must force host dust: the reference dusts
-            # BEFORE remapping (mesh.py:193-198), so labels merged by
-            # the remap pool their voxel counts — device dust would run
-            # after the host remap and see the merged labels. With the
-            # device label map the engine's order is dust -> map, the
-            # reference's order, so both run on the device.
-            device_dust = int(opts['dust_threshold'])
+                and can.dust):
+            # three HIP volume passes instead of a multi-second host
+            # unique/mask at 512^3. A HOST remap must force host dust: the
+            # reference dusts BEFORE remapping (mesh.py:193-198), so labels
+            # merged by the remap pool their voxel counts — device dust
+            # would run after the host remap and see the merged labels.
+            # With the device label map the engine's order is dust -> map,
+            # the reference's order, so both run on the device.
+            call_kw['dust_threshold'] = int(opts['dust_threshold'])
         else:
             data = self._remove_dust(data, opts['dust_threshold'],
                                      opts['dust_global'])
 
-        if label_map is None:
+        if label_map is not None:
+            call_kw['label_map'] = label_map
+        else:
             data = self._remap(data)
             if opts['object_ids']:
                 data = fastremap_np.mask_except(data, opts['object_ids'], in_place=True)
             if opts['exclude_object_ids']:
                 data = fastremap_np.mask(data, opts['exclude_object_ids'], in_place=True)
+        return data[..., 0], call_kw
 
-        data = data[..., 0]
+    def _encode_on_device(self, encode_chunk, data, call_kw, left_offset):
+        """One encode_chunk call -> (binaries, bounding_boxes) by segid.
+        None when a label came back without vertices: the host loop decides
+        what happens then (np.amin raises on it today)."""
+        opts = self.options
+        draco = None
+        if opts['encoding'] == 'draco':
+            draco = dict(self.draco_encoding_settings)
+            # arrives as a numpy float (np.ceil)
+            draco['quantization_bits'] = int(draco['quantization_bits'])
+        encoded = encode_chunk(
+            data, shift=self._global_shift(left_offset),
+            encoding=opts['encoding'], draco=draco, copy=False, **call_kw)
+        if np.any(np.asarray(encoded.nverts) == 0):
+            return None
+        items = list(encoded.items())
+        return ({segid: binary for segid, binary, _ in items},
+                {segid: box for segid, _, box in items})
 
-        mesher = _get_mesher()
-        extra = {}
-        if device_dust:
-            extra['dust_threshold'] = device_dust
-        if label_map is not None:
-            extra['label_map'] = label_map
-
-        # A mesher that advertises encode_chunk returns every label's
-        # finished bytes and box from one call (the engine's device encode
-        # stage) — no Mesh per label, no host loop. Not with fill_holes
-        # (filled and hole meshes are concatenated on the host) nor under
-        # dry_run (the caller wants the meshes).
-        encode_chunk = getattr(mesher, 'encode_chunk', None)
-        if (encode_chunk is not None and fill_level == 0
-                and not opts['dry_run']
-                and opts['encoding'] in getattr(
-                    encode_chunk, 'formats', (opts['encoding'],))):
-            draco = None
-            if opts['encoding'] == 'draco':
-                draco = dict(self.draco_encoding_settings)
-                # arrives as a numpy float (np.ceil)
-                draco['quantization_bits'] = int(draco['quantization_bits'])
-            encoded = encode_chunk(
-                data,
-                resolution=tuple(float(r) for r in self._volume.resolution),
-                reduction_factor=int(opts['simplification_factor'] or 0),
-                max_error=float(opts['max_simplification_error']),
-                voxel_centered=True,
-                shift=self._global_shift(left_offset),
-                encoding=opts['encoding'],
-                draco=draco,
-                copy=False,
-                **extra,
-            )
-            # a label without vertices: the host loop decides what happens
-            # (np.amin raises on it today), so the chunk goes that way
-            if not np.any(np.asarray(encoded.nverts) == 0):
-                del data
-                binaries = {}
-                bounding_boxes = {}
-                for segid, binary, box in encoded.items():
-                    binaries[segid] = binary
-                    bounding_boxes[segid] = box
-                self._upload(binaries, bounding_boxes)
-                return
-
-        # copy=False where supported: this task consumes (shifts, encodes,
-        # uploads) every mesh before its next engine call, so zero-copy
-        # views into the engine's staging buffers are safe — EXCEPT under
-        # dry_run, where the meshes are handed back to the caller and must
-        # own their storage (the reference returns owned arrays).
-        if fill_level:
-            # after dust and the label handling above, host or device
-            # (mesh.py:193-228); the mesher returns (filled, holes)
-            extra['fill_holes'] = fill_level
-        try:
-            raw = mesher(
-                data,
-                resolution=tuple(float(r) for r in self._volume.resolution),
-                reduction_factor=int(opts['simplification_factor'] or 0),
-                max_error=float(opts['max_simplification_error']),
-                voxel_centered=True,
-                copy=bool(opts['dry_run']),
-                **extra,
-            )
-        except TypeError:
-            raw = mesher(
-                data,
-                resolution=tuple(float(r) for r in self._volume.resolution),
-                reduction_factor=int(opts['simplification_factor'] or 0),
-                max_error=float(opts['max_simplification_error']),
-                voxel_centered=True,
-                **extra,
-            )
-        del data
+    def _host_loop(self, raw, fill_level, left_offset):
+        """The mesher's result -> (meshes, binaries, bounding_boxes) by
+        segid: a Mesh per label, shifted, boxed and encoded on the host."""
         hole_raw = {}
         if fill_level:
             raw, hole_raw = raw
@@ -352,16 +370,12 @@ class MeshTask(RegisteredTask):
             else:
                 meshes[segid] = hole_mesh
 
-        bounding_boxes = {}
-        binaries = {}
+        binaries, bounding_boxes = {}, {}
         for segid, mesh in meshes.items():
             binary, mesh_bbx = self._create_mesh_binary(mesh, left_offset)
             binaries[segid] = binary
             bounding_boxes[segid] = mesh_bbx
-
-        if opts['dry_run']:
-            return (meshes, bounding_boxes)
-        self._upload(binaries, bounding_boxes)
+        return meshes, binaries, bounding_boxes
 
     def _upload(self, binaries, bounding_boxes):
         opts = self.options
@@ -425,10 +439,7 @@ class MeshTask(RegisteredTask):
     def _remap(self, data):
         if self.options['remap_table'] is None:
             return data
-        remap_table = {
-            int(k): int(v) for k, v in self.options['remap_table'].items()}
-        self.options['remap_table'] = remap_table
-        remap_table = dict(remap_table)
+        remap_table = dict(self.options['remap_table'])  # ints already
         remap_table[0] = 0
         data = fastremap_np.mask_except(
             data, list(remap_table.keys()), in_place=True)
@@ -517,11 +528,10 @@ import re as _re
 from collections import defaultdict as _defaultdict
 
 
-def MeshManifestFilesystemTask(layer_path: str, lod: int = 0,
-                               mesh_dir=None):
-    """Mirror of the reference's filesystem manifest task
-    (mesh.py:624-670): scan the mesh dir, group fragment files by segid,
-    write {"fragments": [...]} manifests."""
+def _write_manifests(layer_path: str, lod: int, mesh_dir, prefix=None):
+    """Group the mesh dir's fragment files of `lod` (those starting with
+    `prefix`, if given) by segid and write one {"fragments": [...]}
+    manifest per segid."""
     cf = CloudFiles(layer_path)
     info = cf.get_json('info')
     if mesh_dir is None and info and 'mesh' in info:
@@ -529,7 +539,8 @@ def MeshManifestFilesystemTask(layer_path: str, lod: int = 0,
 
     segids = _defaultdict(list)
     regexp = _re.compile(r'(\d+):(\d+):')
-    for name in cf.list(prefix=f"{mesh_dir}/"):
+    for name in cf.list(prefix=f"{mesh_dir}/" if prefix is None
+                        else cf.join(mesh_dir, prefix)):
         filename = name.split("/")[-1]
         matches = _re.search(regexp, filename)
         if not matches:
@@ -542,32 +553,21 @@ def MeshManifestFilesystemTask(layer_path: str, lod: int = 0,
     cf.put_jsons(
         (f"{mesh_dir}/{segid}:{lod}", {"fragments": frags})
         for segid, frags in segids.items())
+
+
+def MeshManifestFilesystemTask(layer_path: str, lod: int = 0,
+                               mesh_dir=None):
+    """Mirror of the reference's filesystem manifest task
+    (mesh.py:624-670): scan the mesh dir, group fragment files by segid,
+    write {"fragments": [...]} manifests."""
+    _write_manifests(layer_path, lod, mesh_dir)
 
 
 def MeshManifestPrefixTask(layer_path: str, prefix: str, lod: int = 0,
                            mesh_dir=None):
     """Mirror of the reference's prefix-parallelized manifest task
     (mesh.py:672-724)."""
-    cf = CloudFiles(layer_path)
-    info = cf.get_json('info')
-    if mesh_dir is None and info and 'mesh' in info:
-        mesh_dir = info['mesh']
-
-    segids = _defaultdict(list)
-    regexp = _re.compile(r'(\d+):(\d+):')
-    for name in cf.list(prefix=cf.join(mesh_dir, prefix)):
-        filename = name.split("/")[-1]
-        matches = _re.search(regexp, filename)
-        if not matches:
-            continue
-        segid, mlod = int(matches.group(1)), int(matches.group(2))
-        if mlod != lod:
-            continue
-        segids[segid].append(filename)
-
-    cf.put_jsons(
-        (f"{mesh_dir}/{segid}:{lod}", {"fragments": frags})
-        for segid, frags in segids.items())
+    _write_manifests(layer_path, lod, mesh_dir, prefix)
 
 
 def TransferMeshFilesTask(src: str, dest: str, prefix: str,

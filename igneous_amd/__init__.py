@@ -14,10 +14,12 @@ from .tasks import (
     MeshTask, MeshManifestPrefixTask, MeshManifestFilesystemTask,
     TransferMeshFilesTask, DeleteMeshFilesTask,
     MultiResShardedMeshMergeTask, MultiResUnshardedMeshMergeTask,
+    CountVoxelsTask,
 )
 from .task_creation import (
     create_meshing_tasks, create_sharded_multires_mesh_tasks,
     create_unsharded_multires_mesh_tasks,
+    create_voxel_counting_tasks, accumulate_voxel_counts,
 )
 from .volume import PrecomputedVolume
 from .lib import Bbox, Vec

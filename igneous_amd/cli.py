@@ -59,6 +59,10 @@ def mesh():
               help="max simplification error in physical units")
 @click.option("--dust-threshold", default=None, type=int,
               help="skip labels smaller than this voxel count")
+@click.option("--dust-global", is_flag=True, default=False,
+              help="apply --dust-threshold to a label's voxel count over "
+                   "the whole dataset, not over one task. Needs `voxels "
+                   "count` and `voxels sum` to have run")
 @click.option("--dir", "mesh_dir", default=None,
               help="mesh subdirectory (overrides info)")
 @click.option("--compress", default="gzip", help="gzip or none")
@@ -80,7 +84,7 @@ def mesh():
 @click.option("--no-execute", is_flag=True, default=False,
               help="only create tasks + mesh info; do not run them")
 def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
-          mesh_dir, compress, spatial_index, sharded, fill_missing,
+          dust_global, mesh_dir, compress, spatial_index, sharded, fill_missing,
           closed_edge, labels, exclude_labels, fill_holes, no_execute):
     """(Re)Generate meshes for the segmentation at PATH
     (reference mesh_forge, cli.py:1035-1071)."""
@@ -90,6 +94,7 @@ def forge(path, queue, mip, shape, simplify, max_error, dust_threshold,
         max_simplification_error=max_error,
         mesh_dir=mesh_dir,
         dust_threshold=dust_threshold,
+        dust_global=dust_global,
         spatial_index=spatial_index,
         sharded=sharded,
         fill_missing=fill_missing,
@@ -158,6 +163,45 @@ def merge_sharded(path, num_lod, vertex_quantization_bits,
     )
     n = execute_tasks(tasks)
     click.echo(f"executed {n} sharded multires merge tasks")
+
+
+@main.group()
+def voxels():
+    """Voxel statistics of a segmentation. (reference cli.py:499-535)"""
+
+
+@voxels.command(name="count")
+@click.argument("path")
+@click.option("--mip", default=0, help="count this mip level")
+@click.option("--fill-missing", is_flag=True, default=False)
+def voxels_count(path, mip, fill_missing):
+    """Count the voxels of every label of PATH in 512^3 tasks, one JSON
+    per task under $KEY/stats/voxel_counts/. Run `voxels sum` afterwards."""
+    from .task_creation import create_voxel_counting_tasks
+    tasks = create_voxel_counting_tasks(path, mip=mip,
+                                        fill_missing=fill_missing)
+    click.echo(f"{len(tasks)} CountVoxelsTasks over {path}")
+    rank, world = rank_world()
+    n = execute_tasks(tasks)
+    click.echo(f"rank {rank}/{world}: executed {n} tasks")
+
+
+@voxels.command(name="sum")
+@click.argument("path")
+@click.option("--mip", default=0, help="sum this mip level's counts")
+@click.option("--compress", default=None, help="gzip or none")
+@click.option("--output", default=None,
+              help="also write the IntMap to this local file")
+def voxels_sum(path, mip, compress, output):
+    """Sum the task counts of `voxels count` into
+    $KEY/stats/voxel_counts.im, which `mesh forge --dust-global` reads
+    (reference cli.py:518-535)."""
+    from .task_creation import accumulate_voxel_counts
+    accumulate_voxel_counts(
+        path, mip=mip, progress=False,
+        compress=(None if compress in (None, "none", "False", "") else compress),
+        additional_output=output)
+    click.echo(f"wrote the voxel counts of {path}")
 
 
 @main.command()

@@ -1010,11 +1010,13 @@ static void set_hole_stash(mg_ctx *c, const ChunkCall &k) {
   c->holes_dtype = k.dtype;
 }
 
-// H2D (skipped when the caller staged the identical volume already)
+// H2D (skipped when the caller staged the identical volume already, or
+// mg_count_voxels left it there: MG_FLAG_COUNTED)
 static int upload_labels(mg_ctx *c, const ChunkCall &k,
                          const void *labels_host, uint32_t flags) {
   const size_t bytes = k.nvox * k.esize;
-  if ((flags & MG_FLAG_SKIP_H2D) && c->labels.cap >= bytes) return 0;
+  if ((flags & (MG_FLAG_SKIP_H2D | MG_FLAG_COUNTED)) && c->labels.cap >= bytes)
+    return 0;
   if (ensure_bytes(c, c->labels, bytes)) return 11;
   HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels_host, bytes,
                             hipMemcpyHostToDevice, c->stream), 11);
@@ -1414,7 +1416,8 @@ static int extract_meshset(mg_ctx *c, const ChunkCall &k, uint32_t flags,
 // one destination is set, and which one says how the call ends: `out` in
 // extract_meshset, `bout` (an encoded call, with `ep`) in run_encode.
 struct ChunkRequest {
-  const void *labels;  // host volume; not read under MG_FLAG_SKIP_H2D
+  const void *labels;  // host volume; not read under MG_FLAG_SKIP_H2D /
+                       // MG_FLAG_COUNTED
   int sx, sy, sz, dtype;
   float rx, ry, rz;
   uint32_t reduction_factor;
@@ -1578,6 +1581,30 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
 }
 
 #include "chunk_mesh.hip"
+#include "count_voxels.hip"
+
+// MG_FLAG_COUNTED: the resident volume must be the one the mg_count_voxels
+// call just before left there (`counted`: the stash as this call found it).
+static int check_counted(mg_ctx *c, const ChunkRequest &r, bool counted) {
+  if (r.flags & MG_FLAG_SKIP_H2D) {
+    SET_ERR(c, "MG_FLAG_COUNTED cannot be combined with MG_FLAG_SKIP_H2D");
+    return 9;
+  }
+  if (!counted) {
+    SET_ERR(c, "MG_FLAG_COUNTED: no counted volume on this ctx (it is left "
+            "by mg_count_voxels for the call right after it)");
+    return 9;
+  }
+  if (r.sx != c->counted_sx || r.sy != c->counted_sy ||
+      r.sz != c->counted_sz || r.dtype != c->counted_dtype) {
+    SET_ERR(c, "MG_FLAG_COUNTED: the counted volume is %d x %d x %d dtype %d, "
+            "the call asks for %d x %d x %d dtype %d", c->counted_sx,
+            c->counted_sy, c->counted_sz, c->counted_dtype, r.sx, r.sy, r.sz,
+            r.dtype);
+    return 9;
+  }
+  return 0;
+}
 
 // The argument checks of the four mg_mesh_chunk* calls, in the order their
 // return codes document (the earlier check wins), then mesh_chunk_impl.
@@ -1602,10 +1629,14 @@ static int mesh_chunk_checked(mg_ctx *c, ChunkRequest r) {
   }
   if (r.bout)
     if (int e = check_encode_params(c, r.ep, &r.enc)) return e;
+  const bool counted = c->counted_valid;
   c->holes_valid = false;  // a stash belongs to the call just before
+  c->counted_valid = false;
   if (int e = check_volume_args(c, r.sx, r.sy, r.sz, r.dtype)) return e;
   if (r.map)
     if (int e = check_label_map(c, r.map, r.dtype, r.flags)) return e;
+  if (r.flags & MG_FLAG_COUNTED)
+    if (int e = check_counted(c, r, counted)) return e;
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return mesh_chunk_impl(c, r);
 }
@@ -1676,6 +1707,7 @@ int mg_mesh_holes(mg_ctx *c, float rx, float ry, float rz,
     return 7;
   }
   c->holes_valid = false;  // consumed, also on failure below
+  c->counted_valid = false;
   HIP_TRY(c, hipSetDevice(c->device), 4);
   // the hole volume becomes the resident label volume: no upload
   std::swap(c->labels, c->holes);
@@ -1705,6 +1737,7 @@ int mg_fill_holes(mg_ctx *c, const void *labels, int sx, int sy, int sz,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   const size_t bytes = (size_t)sx * sy * sz * (dtype == MG_U64 ? 8 : 4);
   c->holes_valid = false;  // c->holes is overwritten
+  c->counted_valid = false;  // ... and so is c->labels
   if (ensure_bytes(c, c->labels, bytes)) return 11;
   HIP_TRY(c, hipMemcpyAsync(c->labels.ptr, labels, bytes,
                             hipMemcpyHostToDevice, c->stream), 11);
@@ -1736,6 +1769,7 @@ int mg_simplify_mesh(mg_ctx *c,
     SET_ERR(c, "null argument");
     return 1;
   }
+  c->counted_valid = false;  // a stash belongs to the call just before
   if (ntris > (1u << 31) / 3) {
     SET_ERR(c, "mesh too large (%u tris)", ntris);
     return 2;
@@ -1806,6 +1840,7 @@ int mg_chunk_mesh(mg_ctx *c,
   }
   *out = nullptr;
   *out_order = nullptr;
+  c->counted_valid = false;  // a stash belongs to the call just before
   if (ntris > (1u << 31) / 3) {
     SET_ERR(c, "mesh too large (%u tris)", ntris);
     return 2;

@@ -70,7 +70,8 @@ struct LabelVolume : DevBuf {
 // field carries a value between calls — each is memset or stored on the
 // device inside the call that reads it: the hash words by label_hash_reset
 // (which clears the whole block), map_err by run_label_map, weld_verts by
-// k_total_verts, the simp_* totals by k_last_sum, simp_prof by run_simplify.
+// k_total_verts, the simp_* totals by k_last_sum, simp_prof by run_simplify,
+// cv_cursor by run_count_voxels' own label_hash_reset.
 struct CtxScalars {
   uint32_t lh_counter;       // label hash: next dense id = labels so far
   uint32_t lh_overflow;      // label hash: a probe sequence ran out
@@ -79,6 +80,7 @@ struct CtxScalars {
   uint32_t simp_kept;        // park_inactive / simp_global_round: faces kept
   uint32_t simp_new_verts;   // simp_finalize: referenced vertices
   uint32_t simp_final_tris;  // simp_finalize: final triangle total
+  uint32_t cv_cursor;        // k_count_compact: next (label, count) pair
   unsigned long long simp_prof[6];  // MG_SIMP_PROF phase counters
 };
 // the hash's two words are read back with one 8-byte copy
@@ -181,6 +183,10 @@ struct mg_ctx : DeviceBuffers {
   // consumes it)
   bool holes_valid = false;
   int holes_sx = 0, holes_sy = 0, holes_sz = 0, holes_dtype = 0;
+  // raw volume left resident by the last mg_count_voxels (one chunk call
+  // with MG_FLAG_COUNTED meshes it without an upload)
+  bool counted_valid = false;
+  int counted_sx = 0, counted_sy = 0, counted_sz = 0, counted_dtype = 0;
   uint64_t lh_slots = 1ull << 20;
   // pinned output staging, reused across calls
   HostArr<float> h_verts;

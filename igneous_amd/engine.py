@@ -23,6 +23,10 @@ SO_PATH = os.path.join(_HERE, "csrc", "libmeshgine.so")
 MG_U32, MG_U64 = 0, 1
 MG_FLAG_DEVICE_ONLY = 1
 MG_FLAG_SKIP_H2D = 2
+# the volume is the one the mg_count_voxels call just before left resident
+MG_FLAG_COUNTED = 4
+# mesh_chunk_checked's code for a MG_FLAG_COUNTED call without that volume
+MG_ERR_NOT_COUNTED = 9
 MG_MAP_MISS_KEEP, MG_MAP_MISS_ZERO = 0, 1
 # mg_mesh_chunk_mapped's table cap: larger folds preprocess on the host
 LABEL_MAP_MAX_ENTRIES = 1 << 24
@@ -36,6 +40,7 @@ _EXPORTED_SYMBOLS = [
     "mg_simplify_mesh", "mg_chunk_mesh", "mg_meshset_free",
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
     "mg_mesh_chunk_encoded", "mg_blobset_free",
+    "mg_count_voxels", "mg_label_counts_free",
 ]
 MG_ENC_PRECOMPUTED, MG_ENC_DRACO = 0, 1
 
@@ -138,6 +143,14 @@ class _MgBlobSet(ctypes.Structure):
         ("bbox", ctypes.POINTER(ctypes.c_float)),
         ("blob", ctypes.POINTER(ctypes.c_uint8)),
         ("blob_bytes", ctypes.c_uint64),
+    ]
+
+
+class _MgLabelCounts(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("labels", ctypes.POINTER(ctypes.c_uint64)),
+        ("counts", ctypes.POINTER(ctypes.c_uint64)),
     ]
 
 
@@ -292,6 +305,14 @@ def load_library() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.c_uint32),
         ]
         lib.mg_meshset_free.argtypes = [ctypes.POINTER(_MgMeshSet)]
+        lib.mg_count_voxels.restype = ctypes.c_int
+        lib.mg_count_voxels.argtypes = [
+            ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_uint32,
+            ctypes.POINTER(ctypes.POINTER(_MgLabelCounts)),
+        ]
+        lib.mg_label_counts_free.argtypes = [ctypes.POINTER(_MgLabelCounts)]
         lib.mg_get_stats.restype = ctypes.c_int
         lib.mg_get_stats.argtypes = [ctypes.c_void_p,
                                      ctypes.POINTER(MgStatsEncode)]
@@ -349,6 +370,22 @@ def _engine(device_id: Optional[int]) -> "Engine":
         device_id = int(os.environ.get("MESHGINE_DEVICE",
                                        os.environ.get("LOCAL_RANK", "0")))
     return Engine.get(device_id)
+
+
+def _check_dust_global(dust_global, dust_threshold, skip_h2d) -> None:
+    if dust_global is None:
+        return
+    if dust_threshold:
+        raise ValueError(
+            "dust_global (the global threshold) cannot be combined with "
+            "dust_threshold (the chunk-local one)")
+    if skip_h2d:
+        raise ValueError(
+            "dust_global cannot be combined with skip_h2d: it counts and "
+            "meshes the volume it is given")
+    threshold, lookup = dust_global
+    if int(threshold) < 0 or not callable(lookup):
+        raise ValueError("dust_global: expected (threshold >= 0, lookup)")
 
 
 def _fill_level_unsupported(what: str) -> NotImplementedError:
@@ -412,7 +449,8 @@ class Engine:
                    dust_threshold: int = 0,
                    copy: bool = True,
                    label_map=None,
-                   fill_holes: int = 0):
+                   fill_holes: int = 0,
+                   dust_global=None):
         """GPU counterpart of oracle.mesh_chunk: F-order (sx,sy,sz)
         uint32/uint64 labels -> {label: (verts (V,3) f32 nm, faces (F,3) u32)},
         labels ascending. Under device_only returns {} (stats still filled).
@@ -433,7 +471,17 @@ class Engine:
         PAIR (filled_meshes, hole_meshes): the meshes of the filled volume
         and of the hole volume (mg_mesh_holes, no second upload). Both
         dicts own their storage whatever `copy` says — the second meshing
-        reuses the first one's staging. Not combinable with skip_h2d."""
+        reuses the first one's staging. Not combinable with skip_h2d.
+
+        dust_global=(threshold, lookup) erases every label whose GLOBAL
+        voxel count lookup(labels_u64) -> counts_u64 (a host callable, e.g.
+        formats.intmap.IntMap.lookup of the voxel_counts.im sidecar) is
+        below threshold — the reference's apply_dust_global_threshold
+        (mesh.py:324-355). The chunk's labels come from count_voxels; the
+        dust labels are folded into the label map (dust first, on the raw
+        labels, then the map) and the chunk call meshes the volume the
+        count left resident. Not combinable with dust_threshold (the local
+        threshold) or skip_h2d."""
         fill_holes = int(fill_holes)
         if fill_holes < 0 or fill_holes > 2:
             raise _fill_level_unsupported(f"fill_holes={fill_holes}")
@@ -443,17 +491,25 @@ class Engine:
                 "resident volume has already been filled")
         if fill_holes:
             copy = True
-        args, cmap, _keep = self._chunk_args(
-            labels, resolution, reduction_factor, max_error, voxel_centered,
-            dust_threshold, device_only, skip_h2d, label_map)
-        # the narrowest entry point that takes what was asked for
-        if fill_holes:
-            fn, tail = "mg_mesh_chunk_filled", (cmap, fill_holes)
-        elif cmap is not None:
-            fn, tail = "mg_mesh_chunk_mapped", (cmap,)
-        else:
-            fn, tail = "mg_mesh_chunk", ()
+        _check_dust_global(dust_global, dust_threshold, skip_h2d)
+        labels = np.asfortranarray(labels)
+        # one hold of the lock from the count to the chunk call: no other
+        # thread of this ctx can drop the counted volume in between
         with self._lock:
+            if dust_global is not None:
+                label_map = self._fold_global_dust(
+                    labels, dust_global, label_map)
+            args, cmap, _keep = self._chunk_args(
+                labels, resolution, reduction_factor, max_error,
+                voxel_centered, dust_threshold, device_only, skip_h2d,
+                label_map, counted=dust_global is not None)
+            # the narrowest entry point that takes what was asked for
+            if fill_holes:
+                fn, tail = "mg_mesh_chunk_filled", (cmap, fill_holes)
+            elif cmap is not None:
+                fn, tail = "mg_mesh_chunk_mapped", (cmap,)
+            else:
+                fn, tail = "mg_mesh_chunk", ()
             out = ctypes.POINTER(_MgMeshSet)()
             rc = getattr(self.lib, fn)(*args, *tail, ctypes.byref(out))
             self._check(rc, fn)
@@ -468,17 +524,65 @@ class Engine:
             self._check(rc, "mg_mesh_holes")
             return result, self._collect(out, True)
 
+    def _count_locked(self, labels, skip_h2d: bool = False):
+        """mg_count_voxels of an F-order volume -> (values, counts); the
+        caller holds self._lock."""
+        dtype = _mg_dtype(labels)
+        if labels.ndim != 3:
+            raise ValueError("count_voxels expects a 3-D volume")
+        sx, sy, sz = labels.shape
+        out = ctypes.POINTER(_MgLabelCounts)()
+        rc = self.lib.mg_count_voxels(
+            self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
+            sx, sy, sz, dtype, MG_FLAG_SKIP_H2D if skip_h2d else 0,
+            ctypes.byref(out))
+        self._check(rc, "mg_count_voxels")
+        try:
+            n = int(out.contents.n)
+            return (_np_array(out.contents.labels, n, copy=True),
+                    _np_array(out.contents.counts, n, copy=True))
+        finally:
+            self.lib.mg_label_counts_free(out)
+
+    def count_voxels(self, labels: np.ndarray, skip_h2d: bool = False):
+        """Every distinct value of an F-order uint32/uint64 volume and its
+        voxel count on the GPU (mg_count_voxels; fastremap.unique(labels,
+        return_counts=True) of the reference's CountVoxelsTask)
+        -> (values u64[n] ascending, 0 included when present, counts
+        u64[n])."""
+        labels = np.asfortranarray(labels)
+        with self._lock:
+            return self._count_locked(labels, skip_h2d)
+
+    def _fold_global_dust(self, labels, dust_global, label_map):
+        """Count the chunk (the raw volume stays resident), look its labels
+        up in the global table and fold the ones below the threshold into
+        label_map. The caller holds self._lock through the chunk call."""
+        from .remap import fold_dust
+        threshold, lookup = dust_global
+        values, _ = self._count_locked(labels)
+        values = values[values != 0]
+        totals = np.asarray(lookup(values), dtype=np.uint64)
+        if totals.shape != values.shape:
+            raise ValueError("dust_global: lookup must return one count "
+                             "per label")
+        return fold_dust(label_map, values[totals < np.uint64(threshold)],
+                         labels.dtype)
+
     def _chunk_args(self, labels, resolution, reduction_factor, max_error,
                     voxel_centered, dust_threshold, device_only, skip_h2d,
-                    label_map):
+                    label_map, counted: bool = False):
         """The one marshalling of a chunk call: (the _CHUNK_ARGTYPES
         arguments, a reference to the mg_label_map or None, the arrays the
-        two point into — the caller holds them until the call returns)."""
+        two point into — the caller holds them until the call returns).
+        counted: the call follows this volume's mg_count_voxels
+        (MG_FLAG_COUNTED)."""
         labels = np.asfortranarray(labels)
         dtype = _mg_dtype(labels)
         sx, sy, sz = labels.shape
         flags = (MG_FLAG_DEVICE_ONLY if device_only else 0) | \
-                (MG_FLAG_SKIP_H2D if skip_h2d else 0)
+                (MG_FLAG_SKIP_H2D if skip_h2d else 0) | \
+                (MG_FLAG_COUNTED if counted else 0)
         args = (
             self.ctx, labels.ctypes.data_as(ctypes.c_void_p),
             sx, sy, sz, dtype,
@@ -517,7 +621,8 @@ class Engine:
                            draco=None,
                            device_only: bool = False,
                            copy: bool = True,
-                           skip_h2d: bool = False) -> EncodedChunk:
+                           skip_h2d: bool = False,
+                           dust_global=None) -> EncodedChunk:
         """mesh_chunk, ending in every label's finished fragment instead
         of its mesh (mg_mesh_chunk_encoded): for each label, the bytes and
         box MeshTask's host loop makes from mesh_chunk's result for the
@@ -530,7 +635,8 @@ class Engine:
         _origin; other keys are ignored, as the encoder ignores them).
         copy=False leaves the blob a view of this context's pinned
         staging, valid until the next call on this Engine. Under
-        device_only the set is empty (stats still filled)."""
+        device_only the set is empty (stats still filled).
+        dust_global=(threshold, lookup): as in mesh_chunk."""
         if encoding not in ('precomputed', 'draco'):
             raise ValueError(f"encoding {encoding!r}: expected "
                              f"'precomputed' or 'draco'")
@@ -546,10 +652,16 @@ class Engine:
             if not 0 <= bits < (1 << 32):
                 raise ValueError(f"draco: quantization_bits {bits}")
             params.q_bits = bits
-        args, cmap, _keep = self._chunk_args(
-            labels, resolution, reduction_factor, max_error, voxel_centered,
-            dust_threshold, device_only, skip_h2d, label_map)
+        _check_dust_global(dust_global, dust_threshold, skip_h2d)
+        labels = np.asfortranarray(labels)
         with self._lock:
+            if dust_global is not None:
+                label_map = self._fold_global_dust(
+                    labels, dust_global, label_map)
+            args, cmap, _keep = self._chunk_args(
+                labels, resolution, reduction_factor, max_error,
+                voxel_centered, dust_threshold, device_only, skip_h2d,
+                label_map, counted=dust_global is not None)
             out = ctypes.POINTER(_MgBlobSet)()
             rc = self.lib.mg_mesh_chunk_encoded(
                 *args, cmap, ctypes.byref(params), ctypes.byref(out))
@@ -704,13 +816,14 @@ def mesh_chunk(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                reduction_factor: int = 0, max_error: float = 40.0,
                voxel_centered: bool = True, device_id: Optional[int] = None,
                dust_threshold: int = 0,
-               copy: bool = True, label_map=None, fill_holes: int = 0):
+               copy: bool = True, label_map=None, fill_holes: int = 0,
+               dust_global=None):
     """Module-level product mesher (the default MeshTask path). With
     fill_holes=1|2 returns the pair (filled_meshes, hole_meshes)."""
     return _engine(device_id).mesh_chunk(
         labels, resolution, reduction_factor, max_error, voxel_centered,
         dust_threshold=dust_threshold, copy=copy, label_map=label_map,
-        fill_holes=fill_holes)
+        fill_holes=fill_holes, dust_global=dust_global)
 
 
 # MeshTask checks this to delegate dust_threshold preprocessing to the
@@ -723,6 +836,10 @@ mesh_chunk.handles_label_map = True
 # ... and fill_holes levels 1-2 (device volume pass after dust and the
 # label map; the call then returns (filled_meshes, hole_meshes))
 mesh_chunk.handles_fill_holes = True
+# ... and dust_global=(threshold, lookup): the chunk's labels are counted on
+# the device, looked up in the global voxel counts and the dust folded into
+# the label map
+mesh_chunk.handles_dust_global = True
 
 
 def mesh_chunk_encoded(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
@@ -731,12 +848,13 @@ def mesh_chunk_encoded(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
                        device_id: Optional[int] = None,
                        dust_threshold: int = 0, label_map=None,
                        shift=(0.0, 0.0, 0.0), encoding: str = 'precomputed',
-                       draco=None, copy: bool = True) -> EncodedChunk:
+                       draco=None, copy: bool = True,
+                       dust_global=None) -> EncodedChunk:
     """Module-level encoded mesher: see Engine.mesh_chunk_encoded."""
     return _engine(device_id).mesh_chunk_encoded(
         labels, resolution, reduction_factor, max_error, voxel_centered,
         dust_threshold=dust_threshold, label_map=label_map, shift=shift,
-        encoding=encoding, draco=draco, copy=copy)
+        encoding=encoding, draco=draco, copy=copy, dust_global=dust_global)
 
 
 # ... and that it can return the finished fragments instead of meshes:
@@ -751,6 +869,16 @@ def mesh_chunk_encoded(labels: np.ndarray, resolution=(1.0, 1.0, 1.0),
 # assign ('precomputed', 'draco') here to hand both over.
 mesh_chunk.encode_chunk = mesh_chunk_encoded
 mesh_chunk_encoded.formats = ('draco',)
+
+
+def count_voxels(labels: np.ndarray, device_id: Optional[int] = None):
+    """Module-level voxel counter -> (values, counts); see
+    Engine.count_voxels."""
+    return _engine(device_id).count_voxels(labels)
+
+
+# CountVoxelsTask and MeshTask's host dust_global path find the counter here
+mesh_chunk.count_voxels = count_voxels
 
 
 def fill_holes(labels: np.ndarray, level: int = 1,

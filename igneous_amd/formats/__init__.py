@@ -4,6 +4,8 @@ mapbuffer / DracoPy dependencies exist offline):
 
   mapbuffer  — seung-lab mapbuffer container (MeshTask sharded=True
                fragment files, reference mesh.py:385-397)
+  intmap     — mapbuffer.IntMap stand-in (the global voxel counts,
+               $KEY/stats/voxel_counts.im, reference image.py:2015)
   sharding   — neuroglancer precomputed sharded format
                (neuroglancer_uint64_sharded_v1)
   multilod   — neuroglancer multi-resolution mesh manifest

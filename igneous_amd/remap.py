@@ -108,6 +108,43 @@ def fold_label_ops(remap_table, object_ids, exclude_object_ids, dtype):
     return keys, vals, miss
 
 
+def fold_dust(label_map, dust_ids, dtype):
+    """Fold a set of dust labels into a fold_label_ops table, for the
+    global dust threshold (mesh.py:324-355): the reference erases dust on
+    the RAW labels first and applies remap / object_ids /
+    exclude_object_ids afterwards (mesh.py:193-204), so applying the
+    returned triple equals mask(dust_ids) followed by label_map.
+
+    label_map is None or (keys, vals, miss); dust_ids are raw labels (0 and
+    ids that do not fit dtype can never match a voxel and are dropped).
+      - None: (sorted dust, zeros, 'keep'), or None without dust;
+      - miss 'keep': the table plus {d: 0}, replacing any entry for d;
+      - miss 'zero': the table without the keys in dust (a miss erases)."""
+    top = int(np.iinfo(np.dtype(dtype)).max)
+    dust = np.unique(np.asarray(dust_ids, dtype=np.uint64).reshape(-1))
+    dust = dust[(dust != 0) & (dust <= np.uint64(top))]
+    if label_map is None:
+        if dust.shape[0] == 0:
+            return None
+        return dust, np.zeros_like(dust), 'keep'
+    keys, vals, miss = label_map
+    keys = np.asarray(keys, dtype=np.uint64)
+    vals = np.asarray(vals, dtype=np.uint64)
+    if miss not in ('keep', 'zero'):
+        raise ValueError(f"label_map miss policy {miss!r}: "
+                         f"expected 'keep' or 'zero'")
+    if dust.shape[0] == 0:
+        return keys, vals, miss
+    stay = ~np.isin(keys, dust)
+    keys, vals = keys[stay], vals[stay]
+    if miss == 'keep':
+        keys = np.concatenate([keys, dust])
+        vals = np.concatenate([vals, np.zeros_like(dust)])
+        order = np.argsort(keys, kind='stable')
+        keys, vals = keys[order], vals[order]
+    return keys, vals, miss
+
+
 def unique(data: np.ndarray, return_counts: bool = False):
     """fastremap.unique equivalent (mesh.py:318)."""
     return np.unique(data, return_counts=return_counts)

@@ -9,4 +9,8 @@ from .mesh import (
     create_xfer_meshes_tasks,
     create_sharded_multires_mesh_from_unsharded_tasks,
 )
+from .voxel_counts import (
+    create_voxel_counting_tasks,
+    accumulate_voxel_counts,
+)
 from .common import FinelyDividedTaskIterator, num_tasks

@@ -12,3 +12,4 @@ from .multires import (
     MultiResShardedFromUnshardedMeshMergeTask,
 )
 from .spatial_index import SpatialIndexTask
+from .voxel_counts import CountVoxelsTask

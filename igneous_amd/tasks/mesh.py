@@ -20,6 +20,10 @@ simplified) meshes. When advertised, the same call carries, as device passes:
   - handles_dust / handles_label_map: dust_threshold and the label selection
     (remap_table / object_ids / exclude_object_ids, folded by
     remap.fold_label_ops) — _select_labels decides host or device;
+  - handles_dust_global: dust_threshold with dust_global (mesh.py:324-355):
+    the chunk's labels are counted on the device (mg_count_voxels), looked
+    up in the voxel_counts.im sidecar that accumulate_voxel_counts wrote, and
+    the labels below the threshold folded into the label map;
   - handles_fill_holes: fill_holes levels 1-2 (mesh.py:211-243) after dust
     and the selection; the filled and the hole volume's meshes come back
     and are concatenated per segment id;
@@ -36,11 +40,11 @@ Deliberate deviations (documented in DESIGN.md):
     a latent NameError).
   - fill_holes 1-2 follow this repository's own written contract
     (DESIGN.md §7; fastmorph's source is not available to pin against);
-    fill_holes>=3 (multilabel dilation, merge threshold) and dust_global
-    raise NotImplementedError. Sharded output uses the in-repo
-    MapBuffer restatement and draco encoding the in-repo Draco
-    restatement (formats/, byte-level external parity unpinned offline
-    — DESIGN.md §7).
+    fill_holes>=3 (multilabel dilation, merge threshold) raises
+    NotImplementedError. Sharded output uses the in-repo MapBuffer
+    restatement, dust_global the in-repo IntMap restatement and draco
+    encoding the in-repo Draco restatement (formats/, byte-level external
+    parity unpinned offline — DESIGN.md §7).
 """
 from __future__ import annotations
 
@@ -57,6 +61,8 @@ from .. import remap as fastremap_np
 # tests without a GPU (the swapped-in callable is then the *checker's*
 # oracle, never shipped); the default import path is GPU-only.
 _mesher_fn = None
+# {sidecar path: IntMap} of the global voxel counts (dust_global)
+_voxel_counts_cache: dict = {}
 
 
 def set_mesher(fn) -> None:
@@ -67,8 +73,14 @@ def set_mesher(fn) -> None:
     faces)}. fn accepts `copy` (False: the result may alias storage that
     lives until fn's next call) and every keyword it advertises by
     attribute: handles_dust -> dust_threshold=, handles_label_map ->
-    label_map=(keys, vals, miss), handles_fill_holes -> fill_holes= (the
-    result is then the pair (filled, holes)), encode_chunk -> a second
+    label_map=(keys, vals, miss), handles_dust_global ->
+    dust_global=(threshold, lookup) with lookup(labels_u64) -> global voxel
+    counts_u64 (fn erases the chunk's labels below the threshold before the
+    label map; never together with dust_threshold=), handles_fill_holes ->
+    fill_holes= (the result is then the pair (filled, holes)), count_voxels
+    -> a callable (3-D labels) -> (values, counts) as np.unique gives them
+    (CountVoxelsTask, and dust_global where the label map stays on the
+    host), encode_chunk -> a second
     callable taking the same keywords plus shift= / encoding= / draco= and
     returning an engine.EncodedChunk, for the encodings its `formats` lists
     (all, if it has none). What fn raises, TypeError included, reaches
@@ -91,6 +103,8 @@ class _Capabilities:
         self.dust = getattr(mesher, 'handles_dust', False)
         self.label_map = getattr(mesher, 'handles_label_map', False)
         self.fill_holes = getattr(mesher, 'handles_fill_holes', False)
+        self.dust_global = getattr(mesher, 'handles_dust_global', False)
+        self.count_voxels = getattr(mesher, 'count_voxels', None)
         self.encode_chunk = getattr(mesher, 'encode_chunk', None)
         self.formats = getattr(self.encode_chunk, 'formats', None)
 
@@ -305,7 +319,33 @@ class MeshTask(RegisteredTask):
                     label_map = None
 
         call_kw = {}
-        if (opts['dust_threshold'] and not opts['dust_global']
+        if opts['dust_threshold'] and opts['dust_global']:
+            # the global threshold: a label is dust by its voxel count over
+            # the whole dataset, not over this chunk (mesh.py:324-355)
+            if not can.dust_global:
+                raise NotImplementedError(
+                    "dust_global needs a mesher that takes the global "
+                    "voxel counts (handles_dust_global): the HIP engine "
+                    "does, the injected mesher does not")
+            lookup = self._global_voxel_counts().lookup
+            threshold = int(opts['dust_threshold'])
+            host_map = (opts['remap_table'] is not None or opts['object_ids']
+                        or opts['exclude_object_ids']) and label_map is None
+            if can.label_map and not host_map:
+                call_kw['dust_global'] = (threshold, lookup)
+            else:
+                # the label map stays on the host, and dust comes before
+                # it: count on the device, mask here
+                if can.count_voxels is None:
+                    raise NotImplementedError(
+                        "dust_global with a host label selection needs the "
+                        "mesher's count_voxels")
+                values, _ = can.count_voxels(data[..., 0])
+                values = np.asarray(values, dtype=np.uint64)
+                values = values[values != 0]
+                dust = values[lookup(values) < np.uint64(threshold)]
+                data = fastremap_np.mask(data, dust.tolist(), in_place=True)
+        elif (opts['dust_threshold']
                 and (opts['remap_table'] is None or label_map is not None)
                 and can.dust):
             # three HIP volume passes instead of a multi-second host
@@ -317,8 +357,7 @@ class MeshTask(RegisteredTask):
             # the reference's order, so both run on the device.
             call_kw['dust_threshold'] = int(opts['dust_threshold'])
         else:
-            data = self._remove_dust(data, opts['dust_threshold'],
-                                     opts['dust_global'])
+            data = self._remove_dust(data, opts['dust_threshold'])
 
         if label_map is not None:
             call_kw['label_map'] = label_map
@@ -424,13 +463,26 @@ class MeshTask(RegisteredTask):
             return self._volume.info['mesh']
         raise ValueError("The mesh destination is not present in the info file.")
 
-    def _remove_dust(self, data, dust_threshold, dust_global):
+    def _global_voxel_counts(self):
+        """The dataset's voxel_counts.im sidecar (mesh.py:325-345), parsed
+        once per process and path."""
+        from .voxel_counts import voxel_counts_sidecar
+        name = voxel_counts_sidecar(self._volume.key)
+        path = f"{self._volume.cloudpath}/{name}"
+        counts = _voxel_counts_cache.get(path)
+        if counts is None:
+            buf = CloudFiles(self._volume.cloudpath).get(name)
+            if buf is None:
+                raise FileNotFoundError(
+                    f"Cannot apply global dust threshold without {path}")
+            from ..formats.intmap import IntMap
+            counts = _voxel_counts_cache[path] = IntMap(buf)
+        return counts
+
+    def _remove_dust(self, data, dust_threshold):
+        """The chunk-local threshold on the host (mesh.py:317-320)."""
         if not dust_threshold:
             return data
-        if dust_global:
-            raise NotImplementedError(
-                "dust_global needs the voxel_counts.im sidecar "
-                "(mesh.py:324-355); out of hot-path scope")
         segids, pxct = fastremap_np.unique(data, return_counts=True)
         dust_segids = [int(sid) for sid, ct in zip(segids, pxct)
                        if ct < int(dust_threshold) and sid != 0]

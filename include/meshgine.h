@@ -46,6 +46,15 @@
  *                        box, and mesh.to_precomputed (mesh.py:448) or
  *                        DracoPy.encode (mesh.py:442-446). Returns every
  *                        label's finished bytes and box.
+ *   mg_count_voxels    — replaces fastremap.unique(labels,
+ *                        return_counts=True) in CountVoxelsTask
+ *                        (/root/reference/igneous/tasks/image/image.py:876)
+ *                        and the per-chunk fastremap.unique of
+ *                        MeshTask.apply_dust_global_threshold (mesh.py:346):
+ *                        every value of the volume with its voxel count,
+ *                        from one device pass. The volume stays resident, so
+ *                        the chunk call that follows (MG_FLAG_COUNTED) meshes
+ *                        it without a second upload.
  *   mg_meshset_free    — replaces Python GC of zmesh.Mesh objects.
  *   mg_last_error      — error text for the last failed call on this ctx.
  *
@@ -93,6 +102,18 @@ typedef struct mg_ctx mg_ctx;
                                    call with identical dims/dtype (bench:
                                    timed region starts with inputs in
                                    HBM). Caller's responsibility. */
+#define MG_FLAG_COUNTED     4u  /* the four mg_mesh_chunk* calls: the label
+                                   volume is the RAW one the mg_count_voxels
+                                   call JUST BEFORE on this ctx left
+                                   resident; no upload. Unlike
+                                   MG_FLAG_SKIP_H2D it may be combined with
+                                   a label map and with fill_level > 0 (the
+                                   volume is known to be raw). Checked after
+                                   every other argument check, return code
+                                   9: no counted volume on the ctx (any
+                                   other call in between drops it), dims or
+                                   dtype differ from the counted volume's,
+                                   or combined with MG_FLAG_SKIP_H2D. */
 
 /* One label's mesh. verts = 3*nverts float32 chunk-local nm (x,y,z);
  * faces = 3*ntris uint32 indices into verts. Pointers alias the meshset's
@@ -322,6 +343,34 @@ int mg_fill_holes(mg_ctx *ctx, const void *labels,
                   void *filled_out, void *holes_out, uint32_t *rounds_out);
 
 void mg_meshset_free(mg_meshset *ms);
+
+/* Every distinct value of a label volume with its voxel count. labels[]
+ * is ascending and includes 0 when the volume holds a 0 (as
+ * fastremap.unique does); counts[i] voxels carry labels[i]. Both tables
+ * live in the descriptor allocation, which mg_label_counts_free frees. */
+typedef struct {
+  uint64_t  n;
+  uint64_t *labels;      /* [n] ascending */
+  uint64_t *counts;      /* [n] */
+} mg_label_counts;
+
+/* Count the voxels of every label of an F-order volume (arguments as
+ * mg_mesh_chunk). One device pass over runs of equal values builds the
+ * label table and the histogram together; the count of 0 is the remainder.
+ * flags: MG_FLAG_SKIP_H2D keeps its meaning, other bits are ignored.
+ * Errors, in this order: NULL ctx / labels / out (1), dims outside 1..2047
+ * (2), bad dtype (3), 2^32 or more voxels (2: device counts are 32-bit).
+ * The ctx stays usable after any of them. On success the RAW volume stays
+ * resident for the next call on the ctx, which may be an mg_mesh_chunk*
+ * with MG_FLAG_COUNTED; the call drops a stashed hole volume.
+ * mg_get_stats afterwards: ms_h2d, ms_count (the histogram pass, or
+ * passes when the label table had to grow), ms_total, n_labels (distinct
+ * non-zero labels) and bytes_read_algorithmic; every other field is 0. */
+int mg_count_voxels(mg_ctx *ctx, const void *labels,
+                    int sx, int sy, int sz, int dtype, uint32_t flags,
+                    mg_label_counts **out);
+
+void mg_label_counts_free(mg_label_counts *lc);
 
 /* Quadric edge-collapse simplification of ONE standalone mesh on the
  * GPU — the simplifier reused at merge granularity: replaces

@@ -743,22 +743,57 @@ static const uint32_t *cm_cells_view(const uint32_t *cells, int f,
   return cells + f * stride;
 }
 
+// The per-cell table on the host and what both result stages derive from
+// it: the cells that hold faces and the host function's dict order.
+struct CmCellTable {
+  std::vector<uint32_t> cells;  // copy of c->cm_cells
+  const uint32_t *dense, *firstp, *vb, *fb;  // views, entry ncellp = totals
+  std::vector<uint32_t> live;   // cell ordinals with faces, ascending
+  std::vector<uint32_t> order;  // indices into live, dict order
+  uint64_t V, F;                // vertex / face totals over all cells
+};
+
+// [7a] read the per-cell table (one sync) and derive the dict order: cells
+// whose stream starts with an interior face (sort key bit 0 clear) in
+// ascending cell order, then the rest by first emitted pair
+static int cm_read_cells(mg_ctx *c, const CmCall &k, CmCellTable &t) {
+  hipStream_t s = c->stream;
+  const uint64_t stride = (uint64_t)k.ncellp + 1;
+  t.cells.resize(stride * CM_CELL_FIELDS);
+  HIP_TRY(c, hipMemcpyAsync(t.cells.data(), c->cm_cells.get(),
+                            t.cells.size() * 4, hipMemcpyDeviceToHost, s), 73);
+  HIP_TRY(c, hipStreamSynchronize(s), 73);
+  t.dense = cm_cells_view(t.cells.data(), CM_CELL_DENSE, stride);
+  t.firstp = cm_cells_view(t.cells.data(), CM_CELL_FIRSTP, stride);
+  t.vb = cm_cells_view(t.cells.data(), CM_CELL_VB, stride);
+  t.fb = cm_cells_view(t.cells.data(), CM_CELL_FB, stride);
+  t.V = t.vb[k.ncellp];
+  t.F = t.fb[k.ncellp];
+  t.live.clear();
+  for (uint32_t o = 0; o < k.ncellp; ++o)
+    if (t.fb[o + 1] > t.fb[o]) t.live.push_back(o);
+  t.order.resize(t.live.size());
+  for (uint32_t m = 0; m < t.order.size(); ++m) t.order[m] = m;
+  std::stable_sort(t.order.begin(), t.order.end(),
+                   [&](uint32_t a, uint32_t b) {
+    uint32_t oa = t.live[a], ob = t.live[b];
+    bool ia = !(t.dense[oa] & 1u), ib = !(t.dense[ob] & 1u);
+    if (ia != ib) return ia;
+    if (ia) return oa < ob;
+    return t.firstp[oa] < t.firstp[ob];
+  });
+  return 0;
+}
+
 // [7] D2H into the ctx's pinned staging + the descriptor: one mesh per
 // non-empty cell by ascending label (= lexicographic cell order), and the
 // host function's dict order in out_order[nmeshes] behind nf_arr.
 static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
                       const uint32_t **out_order) {
   hipStream_t s = c->stream;
-  const uint64_t stride = (uint64_t)k.ncellp + 1;
-  std::vector<uint32_t> cells(stride * CM_CELL_FIELDS);
-  HIP_TRY(c, hipMemcpyAsync(cells.data(), c->cm_cells.get(),
-                            cells.size() * 4, hipMemcpyDeviceToHost, s), 73);
-  HIP_TRY(c, hipStreamSynchronize(s), 73);
-  const uint32_t *dense = cm_cells_view(cells.data(), CM_CELL_DENSE, stride);
-  const uint32_t *firstp = cm_cells_view(cells.data(), CM_CELL_FIRSTP, stride);
-  const uint32_t *vb = cm_cells_view(cells.data(), CM_CELL_VB, stride);
-  const uint32_t *fb = cm_cells_view(cells.data(), CM_CELL_FB, stride);
-  const uint64_t V = vb[k.ncellp], F = fb[k.ncellp];
+  CmCellTable t;
+  if (int e = cm_read_cells(c, k, t)) return e;
+  const uint64_t V = t.V, F = t.F;
   if (ensure(c, c->h_verts, 3 * V + 3)) return 73;
   if (ensure(c, c->h_faces, 3 * F + 3)) return 73;
   float *h_verts = c->h_verts.get();
@@ -771,10 +806,7 @@ static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
                               hipMemcpyDeviceToHost, s), 73);
   HIP_TRY(c, hipStreamSynchronize(s), 73);
 
-  std::vector<uint32_t> live;  // cell ordinals with faces, ascending
-  for (uint32_t o = 0; o < k.ncellp; ++o)
-    if (fb[o + 1] > fb[o]) live.push_back(o);
-  const uint32_t n = (uint32_t)live.size();
+  const uint32_t n = (uint32_t)t.live.size();
   mg_meshset *ms = alloc_meshset(n, 1);
   if (!ms) {
     SET_ERR(c, "chunk_mesh: out of host memory");
@@ -786,40 +818,32 @@ static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
   ms->total_verts = V;
   ms->total_tris = F;
   for (uint32_t m = 0; m < n; ++m) {
-    uint32_t o = live[m];
-    uint32_t d = dense[o] >> 1;
+    uint32_t o = t.live[m];
+    uint32_t d = t.dense[o] >> 1;
     int64_t cz = (int64_t)(d % k.dn.nz) + k.dn.lo[2];
     int64_t cy = (int64_t)((d / k.dn.nz) % k.dn.ny) + k.dn.lo[1];
     int64_t cx = (int64_t)(d / k.dn.nz / k.dn.ny) + k.dn.lo[0];
     const uint64_t label = ((uint64_t)(cx + (1 << 20)) << 42) |
                            ((uint64_t)(cy + (1 << 20)) << 21) |
                            (uint64_t)(cz + (1 << 20));
-    set_mesh(ms, m, label, vb[o], vb[o + 1] - vb[o], fb[o],
-             fb[o + 1] - fb[o]);
-    order[m] = m;
+    set_mesh(ms, m, label, t.vb[o], t.vb[o + 1] - t.vb[o], t.fb[o],
+             t.fb[o + 1] - t.fb[o]);
+    order[m] = t.order[m];
   }
-  // dict order: cells whose stream starts with an interior face (sort key
-  // bit 0 clear) in ascending cell order, then the rest by first emitted
-  // pair
-  std::stable_sort(order, order + n, [&](uint32_t a, uint32_t b) {
-    uint32_t oa = live[a], ob = live[b];
-    bool ia = !(dense[oa] & 1u), ib = !(dense[ob] & 1u);
-    if (ia != ib) return ia;
-    if (ia) return oa < ob;
-    return firstp[oa] < firstp[ob];
-  });
   *out = ms;
   *out_order = order;
   return 0;
 }
 
-static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
-                          const uint32_t *faces, uint32_t ntris,
-                          const double scale[3], const double offset[3],
-                          mg_meshset **out, const uint32_t **out_order) {
+// [0]..[6]: everything up to the per-cell output slices in cm_out_v /
+// cm_out_f and the per-cell table in cm_cells, all left on the device
+static int cm_run_device(mg_ctx *c, CmCall &k, const float *verts,
+                         uint32_t nverts, const uint32_t *faces,
+                         uint32_t ntris, const double scale[3],
+                         const double offset[3]) {
   if (int e = cm_validate(c, verts, nverts, faces, ntris, scale, offset))
     return e;
-  CmCall k = {};
+  k = {};
   k.nverts = nverts;
   k.ntris = ntris;
   for (int a = 0; a < 3; ++a) {
@@ -837,6 +861,15 @@ static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
   if (int e = cm_emit(c, k, keys.current(), vals.current())) return e;
   if (k.C > 0)
     if (int e = cm_weld(c, k)) return e;
-  if (int e = cm_faces(c, k, vals.current())) return e;
+  return cm_faces(c, k, vals.current());
+}
+
+static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
+                          const uint32_t *faces, uint32_t ntris,
+                          const double scale[3], const double offset[3],
+                          mg_meshset **out, const uint32_t **out_order) {
+  CmCall k;
+  if (int e = cm_run_device(c, k, verts, nverts, faces, ntris, scale, offset))
+    return e;
   return cm_extract(c, k, out, out_order);
 }

@@ -1581,6 +1581,7 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
 }
 
 #include "chunk_mesh.hip"
+#include "merge_verts.hip"
 #include "count_voxels.hip"
 
 // MG_FLAG_COUNTED: the resident volume must be the one the mg_count_voxels
@@ -1855,6 +1856,82 @@ int mg_chunk_mesh(mg_ctx *c,
   HIP_TRY(c, hipSetDevice(c->device), 4);
   return run_chunk_mesh(c, verts, nverts, faces, ntris, scale, offset, out,
                         out_order);
+}
+
+// the argument checks the two weld entry points share (the ctx is locked)
+static int check_weld_args(mg_ctx *c, const float *verts, uint32_t nverts,
+                           const uint32_t *faces, uint32_t ntris,
+                           const float **out_verts, uint32_t *out_nverts,
+                           const uint32_t **out_faces, uint32_t *out_ntris) {
+  if (!out_verts || !out_nverts || !out_faces || !out_ntris ||
+      (nverts > 0 && !verts) || (ntris > 0 && !faces)) {
+    SET_ERR(c, "null argument");
+    return 1;
+  }
+  *out_verts = nullptr;
+  *out_faces = nullptr;
+  *out_nverts = 0;
+  *out_ntris = 0;
+  c->counted_valid = false;  // a stash belongs to the call just before
+  if (ntris > (1u << 31) / 3 || nverts > (1u << 31)) {
+    SET_ERR(c, "mesh too large (%u vertices, %u tris)", nverts, ntris);
+    return 2;
+  }
+  return 0;
+}
+
+// Weld the vertices of one mesh that lie within `radius` of each other
+// (multires merge; see meshgine.h). The pipeline is in merge_verts.hip.
+int mg_merge_close_vertices(mg_ctx *c,
+                            const float *verts, uint32_t nverts,
+                            const uint32_t *faces, uint32_t ntris,
+                            double radius,
+                            const float **out_verts, uint32_t *out_nverts,
+                            const uint32_t **out_faces, uint32_t *out_ntris) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (int e = check_weld_args(c, verts, nverts, faces, ntris, out_verts,
+                              out_nverts, out_faces, out_ntris))
+    return e;
+  HIP_TRY(c, hipSetDevice(c->device), 4);
+  return run_merge_close_host(c, verts, nverts, faces, ntris, radius,
+                              out_verts, out_nverts, out_faces, out_ntris);
+}
+
+// Grid-chunk one mesh, concatenate the cells and weld them, all on the
+// device (multires merge; see meshgine.h).
+int mg_retriangulate_mesh(mg_ctx *c,
+                          const float *verts, uint32_t nverts,
+                          const uint32_t *faces, uint32_t ntris,
+                          const double scale[3], const double offset[3],
+                          double radius,
+                          const float **out_verts, uint32_t *out_nverts,
+                          const uint32_t **out_faces, uint32_t *out_ntris) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (!scale || !offset) { SET_ERR(c, "null argument"); return 1; }
+  if (int e = check_weld_args(c, verts, nverts, faces, ntris, out_verts,
+                              out_nverts, out_faces, out_ntris))
+    return e;
+  bool no_cells = true;
+  if (ntris > 0) {
+    HIP_TRY(c, hipSetDevice(c->device), 4);
+    if (int e = run_retriangulate(c, verts, nverts, faces, ntris, scale,
+                                  offset, radius, &no_cells, out_verts,
+                                  out_nverts, out_faces, out_ntris))
+      return e;
+  } else if (int e = mv_check_radius(c, radius)) {
+    return e;
+  }
+  if (no_cells) {  // the input is the result: NULL arrays, its counts
+    *out_verts = nullptr;
+    *out_faces = nullptr;
+    *out_nverts = nverts;
+    *out_ntris = ntris;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -89,6 +89,7 @@ static_assert(offsetof(CtxScalars, lh_overflow) ==
 
 struct SimpPlane;  // simplify.hip
 struct CmMisc;     // chunk_mesh.hip
+struct MvMisc;     // merge_verts.hip
 
 // Every device buffer of a context (grow-only cache). This is the one
 // list: ~mg_ctx releases the struct as a whole.
@@ -139,6 +140,15 @@ struct DeviceBuffers {
       cm_cells,  // carved: CM_CELL_FIELDS arrays of one stride
       cm_wkey, cm_wkey_alt, cm_wval, cm_wval_alt, cm_whead, cm_wrun,
       cm_head_pos, cm_rep, cm_keep, cm_used, cm_vid, cm_fslot, cm_out_f;
+  // merge_close_vertices / retriangulate (merge_verts.hip): the mesh to
+  // weld, per-vertex cells and union-find parents, the grid sort's double
+  // buffers, flags and scans, outputs, the retriangulation's gather table
+  DevArr<MvMisc> mv_misc;
+  DevArr<float> mv_verts, mv_out_v;
+  DevArr<long long> mv_cell;  // 3 per vertex
+  DevArr<uint32_t> mv_faces, mv_key, mv_key_alt, mv_val, mv_val_alt,
+      mv_parent, mv_keep, mv_used, mv_vid, mv_fslot, mv_out_f,
+      mv_tab;  // carved: MV_TAB_FIELDS arrays of one stride
   // encode (encode.hip): per-label entry sizes / offsets / varint index
   // bytes, box words (order-preserving u32) and boxes (f32), the blob
   DevArr<uint64_t> enc_size, enc_off, enc_ilen;

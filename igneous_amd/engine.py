@@ -41,6 +41,7 @@ _EXPORTED_SYMBOLS = [
     "mg_get_stats", "mg_last_error", "mg_device_count", "mg_version",
     "mg_mesh_chunk_encoded", "mg_blobset_free",
     "mg_count_voxels", "mg_label_counts_free",
+    "mg_merge_close_vertices", "mg_retriangulate_mesh",
 ]
 MG_ENC_PRECOMPUTED, MG_ENC_DRACO = 0, 1
 
@@ -340,6 +341,28 @@ def load_library() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.POINTER(_MgMeshSet)),
             ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
         ]
+        # the four result arguments of mg_simplify_mesh and the two welds
+        mesh_out = [
+            ctypes.POINTER(ctypes.POINTER(ctypes.c_float)),
+            ctypes.POINTER(ctypes.c_uint32),
+            ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)),
+            ctypes.POINTER(ctypes.c_uint32),
+        ]
+        lib.mg_merge_close_vertices.restype = ctypes.c_int
+        lib.mg_merge_close_vertices.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_double,
+        ] + mesh_out
+        lib.mg_retriangulate_mesh.restype = ctypes.c_int
+        lib.mg_retriangulate_mesh.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+            ctypes.c_double,
+        ] + mesh_out
         _lib = lib
         return lib
 
@@ -804,6 +827,55 @@ class Engine:
             result[key] = by_label[lab]
         return result
 
+    def _weld_call(self, fn: str, verts, faces, radius, *grid):
+        """mg_merge_close_vertices / mg_retriangulate_mesh (grid = its
+        scale and offset) -> owned (verts, faces), copied under the lock."""
+        radius = float(radius)
+        if not np.isfinite(radius) or radius <= 0:
+            raise ValueError(f"radius {radius}: must be finite and > 0")
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+        grid = [(ctypes.c_double * 3)(*[float(x) for x in g]) for g in grid]
+        ov = ctypes.POINTER(ctypes.c_float)()
+        of = ctypes.POINTER(ctypes.c_uint32)()
+        onv = ctypes.c_uint32()
+        ont = ctypes.c_uint32()
+        # the results are views of the ctx's pinned staging: hold the lock
+        # until they are copied, or another thread's call overwrites them
+        with self._lock:
+            rc = getattr(self.lib, fn)(
+                self.ctx,
+                v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
+                f.ctypes.data_as(ctypes.c_void_p), f.shape[0],
+                *grid, radius,
+                ctypes.byref(ov), ctypes.byref(onv),
+                ctypes.byref(of), ctypes.byref(ont))
+            self._check(rc, fn)
+            if not ov:  # mg_retriangulate_mesh: no cell, the input stands
+                return v.copy(), f.copy()
+            return (_np_array(ov, onv.value, 3, copy=True),
+                    _np_array(of, ont.value, 3, copy=True))
+
+    def merge_close_vertices(self, verts: np.ndarray, faces: np.ndarray,
+                             radius: float = 1e-5):
+        """Weld the vertices within `radius` of each other on the GPU
+        (mg_merge_close_vertices; the Mesh.merge_close_vertices replacement
+        of multires.py:551, bit-equal to meshops.merge_close_vertices).
+        Returns owned (verts, faces)."""
+        return self._weld_call("mg_merge_close_vertices", verts, faces,
+                               radius)
+
+    def retriangulate_mesh(self, verts: np.ndarray, faces: np.ndarray,
+                           scale, offset, radius: float = 1e-5):
+        """Cut one mesh at the grid's cell boundaries and weld the pieces
+        on the GPU (mg_retriangulate_mesh; retriangulate_mesh of
+        multires.py:546-553): bit-equal to meshops.merge_close_vertices of
+        the concatenated meshops.chunk_mesh cells, which never leave the
+        device. A mesh the chunker keeps no cell of comes back unchanged.
+        Returns owned (verts, faces)."""
+        return self._weld_call("mg_retriangulate_mesh", verts, faces, radius,
+                               scale, offset)
+
     def stats(self) -> dict:
         s = MgStatsEncode()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
@@ -895,6 +967,27 @@ def chunk_mesh(mesh, scale, offset, device_id: Optional[int] = None):
     cells = _engine(device_id).chunk_mesh(
         mesh.vertices, mesh.faces, scale, offset)
     return {key: Mesh(v, f, id=mesh.id) for key, (v, f) in cells.items()}
+
+
+def merge_close_vertices(mesh, radius: float = 1e-5,
+                         device_id: Optional[int] = None):
+    """Module-level vertex weld: Mesh -> Mesh, the result of
+    meshops.merge_close_vertices."""
+    from .meshes import Mesh
+    v, f = _engine(device_id).merge_close_vertices(
+        mesh.vertices, mesh.faces, radius)
+    return Mesh(v, f, id=mesh.id)
+
+
+def retriangulate_mesh(mesh, scale, offset, radius: float = 1e-5,
+                       device_id: Optional[int] = None):
+    """Module-level retriangulation (the default multires path): Mesh ->
+    Mesh, chunk_mesh + Mesh.concatenate + merge_close_vertices in one
+    device call."""
+    from .meshes import Mesh
+    v, f = _engine(device_id).retriangulate_mesh(
+        mesh.vertices, mesh.faces, scale, offset, radius)
+    return Mesh(v, f, id=mesh.id)
 
 
 def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,

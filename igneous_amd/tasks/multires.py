@@ -16,7 +16,10 @@ specs/algorithms — DESIGN.md §7):
   zmesh.chunk_mesh                        -> the HIP engine's chunk_mesh
         via the `set_chunker` seam (igneous_amd.meshops.chunk_mesh is the
         bit-equal CPU checker)
-  merge_close_vertices                    -> igneous_amd.meshops
+  retriangulate_mesh's chunk_mesh + concatenate + merge_close_vertices
+                                          -> the HIP engine's
+        retriangulate_mesh via the `set_retriangulator` seam (the host
+        composition over igneous_amd.meshops is the bit-equal CPU checker)
   zmesh.simplify_fqmr                     -> the HIP quadric simplifier
         via the `set_simplifier` seam (default: engine.simplify_mesh on
         the GPU; the pyfqmr aggressiveness/K error schedule is NOT
@@ -58,6 +61,7 @@ __all__ = [
     "generate_lods",
     "set_simplifier",
     "set_chunker",
+    "set_retriangulator",
 ]
 
 # ---------------------------------------------------------------------------
@@ -107,6 +111,43 @@ def _get_chunker():
         return meshops.chunk_mesh
     from .. import engine
     return engine.chunk_mesh
+
+
+# Retriangulator seam, beside the chunker's and under the same rule: an
+# injected retriangulator wins; with an injected chunker or simplifier the
+# host composition runs (_get_chunker(), Mesh.concatenate,
+# meshops.merge_close_vertices); otherwise (the product path) it is the HIP
+# engine's retriangulate_mesh, one device call that is bit-equal to that
+# composition. fn(mesh: Mesh, scale, offset) -> Mesh; a mesh the chunker
+# keeps no cell of comes back as it is.
+
+_retriangulator_fn = None
+
+
+def set_retriangulator(fn) -> None:
+    """Test seam. Pass None to restore the default selection."""
+    global _retriangulator_fn
+    _retriangulator_fn = fn
+
+
+def _host_retriangulate(mesh: Mesh, scale, offset) -> Mesh:
+    chunks = _get_chunker()(mesh, scale, offset)
+    if not chunks:
+        return mesh
+    new_mesh = Mesh.concatenate(*chunks.values(), id=mesh.id)
+    return meshops.merge_close_vertices(new_mesh, radius=1e-5)
+
+
+def _get_retriangulator():
+    if _retriangulator_fn is not None:
+        return _retriangulator_fn
+    if _chunker_fn is not None or _simplifier_fn is not None:
+        return _host_retriangulate
+    from .. import engine
+
+    def gpu_retriangulate(mesh: Mesh, scale, offset) -> Mesh:
+        return engine.retriangulate_mesh(mesh, scale, offset, radius=1e-5)
+    return gpu_retriangulate
 
 
 # ---------------------------------------------------------------------------
@@ -163,11 +204,8 @@ def determine_mesh_shape_from_lods(lods: List[Mesh]):
 def retriangulate_mesh(mesh: Mesh, offset, scale) -> Mesh:
     """Cut triangles at the UPPER octree level's cell boundaries so no
     triangle leaks across a coarser node (multires.py:546-553)."""
-    chunks = _get_chunker()(mesh, scale, offset)
-    if not chunks:
-        return mesh
-    new_mesh = Mesh.concatenate(*chunks.values(), id=mesh.id)
-    return meshops.merge_close_vertices(new_mesh, radius=1e-5)
+    # no chunks: every retriangulator hands the mesh back as it is
+    return _get_retriangulator()(mesh, scale, offset)
 
 
 def cmp_zorder(lhs, rhs) -> int:

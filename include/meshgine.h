@@ -40,6 +40,12 @@
  *   mg_chunk_mesh      — replaces zmesh.chunk_mesh in the multires merge
  *                        (multires.py:550,574): grid partition of one mesh
  *                        with clipping at the cell boundaries.
+ *   mg_merge_close_vertices — replaces Mesh.merge_close_vertices in the
+ *                        multires merge (multires.py:551): weld of the
+ *                        vertices within a radius.
+ *   mg_retriangulate_mesh — replaces retriangulate_mesh as a whole
+ *                        (multires.py:546-553): chunk, concatenate and weld
+ *                        without the cells leaving the device.
  *   mg_mesh_chunk_encoded — mg_mesh_chunk_mapped plus the per-label loop
  *                        that follows it in MeshTask: the shift into
  *                        global nm (mesh.py:434-435), the spatial-index
@@ -424,6 +430,66 @@ int mg_chunk_mesh(mg_ctx *ctx,
                   const uint32_t *faces, uint32_t ntris,
                   const double scale[3], const double offset[3],
                   mg_meshset **out, const uint32_t **out_order);
+
+/* Weld the vertices of ONE mesh that lie within `radius` of each other —
+ * replaces Mesh.merge_close_vertices in the multires merge (the reference's
+ * igneous/tasks/mesh/multires.py:551). Bit-equal to
+ * igneous_amd.meshops.merge_close_vertices (the CPU checker; contract in
+ * DESIGN.md §7a): vertices i and j are close when
+ * dx*dx + dy*dy + dz*dz <= radius*radius in f64; every vertex is replaced
+ * by the smallest index of its connected component of close pairs; faces
+ * with two equal corners are dropped, the rest keep their order; the output
+ * vertices are the representatives a surviving face uses, in ascending
+ * input index, with their own stored bits.
+ *   verts/faces   host arrays (float32 V*3 / uint32 T*3)
+ *   radius        > 0, in the verts' units
+ *   out_*         ctx-owned pinned staging under the mg_simplify_mesh
+ *                 lifetime rule (valid until the next call on the ctx)
+ * A mesh without faces gives 0 vertices and 0 faces.
+ * Return codes, used by these two entry points only (non-zero return +
+ * mg_last_error, never a fault, the ctx stays usable):
+ *   100  rejected before any kernel: a face index >= nverts, a non-finite
+ *        vertex, a radius that is not finite or not > 0
+ *   101  device allocation or upload failed
+ *   102  the grid stage (cells, sort, candidate count) failed
+ *   103  rejected by the grid stage: a coordinate with |v / (2*radius)| >=
+ *        2^51, or more than 2^32 candidate visits ("radius too large for
+ *        this mesh": the sum, over all vertices, of the vertices sharing a
+ *        grid bucket with one of its 27 neighbour cells of size 2*radius)
+ *   104  the link stage failed      105  the face / vertex stage failed
+ *   106  the download failed        107  the cell gather failed
+ *        (mg_retriangulate_mesh)
+ * besides 1 (null argument), 2 (more than 2^31 vertices or 2^31/3 faces)
+ * and 4 (no device). */
+int mg_merge_close_vertices(mg_ctx *ctx,
+                            const float *verts, uint32_t nverts,
+                            const uint32_t *faces, uint32_t ntris,
+                            double radius,
+                            const float **out_verts, uint32_t *out_nverts,
+                            const uint32_t **out_faces, uint32_t *out_ntris);
+
+/* Cut ONE mesh at a grid's cell boundaries and weld the pieces back into
+ * one mesh — replaces the whole of retriangulate_mesh in the multires merge
+ * (the reference's igneous/tasks/mesh/multires.py:546-553: zmesh.chunk_mesh,
+ * Mesh.concatenate, merge_close_vertices). Bit-equal to
+ * merge_close_vertices(Mesh.concatenate(*chunk_mesh(mesh, scale,
+ * offset).values()), radius) of igneous_amd.meshops, the cells taken in the
+ * checker's dict order (mg_chunk_mesh's out_order). The cells never leave
+ * the device: only the welded mesh is downloaded.
+ *   verts/faces, scale/offset   as mg_chunk_mesh
+ *   radius, out_*               as mg_merge_close_vertices
+ * When the chunker keeps no cell (ntris == 0, or every face degenerate) the
+ * input is the result, as in the reference: the call then sets *out_verts
+ * and *out_faces to NULL and *out_nverts / *out_ntris to the INPUT counts.
+ * A non-NULL *out_verts is always the welded mesh, even an empty one.
+ * Errors: mg_chunk_mesh's (60-73) and mg_merge_close_vertices' (100-107). */
+int mg_retriangulate_mesh(mg_ctx *ctx,
+                          const float *verts, uint32_t nverts,
+                          const uint32_t *faces, uint32_t ntris,
+                          const double scale[3], const double offset[3],
+                          double radius,
+                          const float **out_verts, uint32_t *out_nverts,
+                          const uint32_t **out_faces, uint32_t *out_ntris);
 
 /* Stats of the last mg_mesh_chunk on this ctx. Returns 0 on success. */
 int mg_get_stats(mg_ctx *ctx, mg_stats *out);

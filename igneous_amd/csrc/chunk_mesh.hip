@@ -521,13 +521,30 @@ static int cm_validate(mg_ctx *c, const float *verts, uint32_t nverts,
   return 0;
 }
 
-// [1] upload, per-face cell ranges, pair offsets, cell bounding box
-static int cm_count(mg_ctx *c, CmCall &k, const float *verts,
-                    const uint32_t *faces) {
+// room for a mesh of V vertices and T faces in cm_verts / cm_faces
+static int cm_ensure_input(mg_ctx *c, uint64_t V, uint64_t T) {
+  if (ensure(c, c->cm_verts, 3 * V + 3)) return 61;
+  if (ensure(c, c->cm_faces, 3 * T + 3)) return 61;
+  return 0;
+}
+
+// [0] upload of the caller's mesh into cm_verts / cm_faces
+static int cm_upload(mg_ctx *c, const float *verts, uint32_t nverts,
+                     const uint32_t *faces, uint32_t ntris) {
+  hipStream_t s = c->stream;
+  if (int e = cm_ensure_input(c, nverts, ntris)) return e;
+  HIP_TRY(c, hipMemcpyAsync(c->cm_verts.get(), verts, (uint64_t)nverts * 12,
+                            hipMemcpyHostToDevice, s), 61);
+  HIP_TRY(c, hipMemcpyAsync(c->cm_faces.get(), faces, (uint64_t)ntris * 12,
+                            hipMemcpyHostToDevice, s), 61);
+  return 0;
+}
+
+// [1] per-face cell ranges, pair offsets, cell bounding box of the mesh in
+// cm_verts / cm_faces
+static int cm_count(mg_ctx *c, CmCall &k) {
   hipStream_t s = c->stream;
   const uint64_t T = k.ntris;
-  if (ensure(c, c->cm_verts, 3 * (uint64_t)k.nverts + 3)) return 61;
-  if (ensure(c, c->cm_faces, 3 * T + 3)) return 61;
   if (ensure(c, c->cm_ncells, T + 1)) return 61;
   if (ensure(c, c->cm_pair_off, T + 1)) return 61;
   if (ensure(c, c->cm_misc, 1)) return 61;
@@ -537,11 +554,6 @@ static int cm_count(mg_ctx *c, CmCall &k, const float *verts,
     init.bb_hi[a] = INT32_MIN;
   }
   HIP_TRY(c, hipMemcpyAsync(c->cm_misc.get(), &init, sizeof(init),
-                            hipMemcpyHostToDevice, s), 61);
-  HIP_TRY(c, hipMemcpyAsync(c->cm_verts.get(), verts,
-                            (uint64_t)k.nverts * 12, hipMemcpyHostToDevice,
-                            s), 61);
-  HIP_TRY(c, hipMemcpyAsync(c->cm_faces.get(), faces, T * 12,
                             hipMemcpyHostToDevice, s), 61);
   hipLaunchKernelGGL(k_cm_face_count, dim3(cm_blocks(T + 1)), dim3(CM_BLK), 0,
                      s, c->cm_verts.get(), c->cm_faces.get(), k.ntris, k.g,
@@ -835,14 +847,12 @@ static int cm_extract(mg_ctx *c, const CmCall &k, mg_meshset **out,
   return 0;
 }
 
-// [0]..[6]: everything up to the per-cell output slices in cm_out_v /
+// [1]..[6] on the mesh in cm_verts / cm_faces (finite vertices, indices <
+// nverts): everything up to the per-cell output slices in cm_out_v /
 // cm_out_f and the per-cell table in cm_cells, all left on the device
-static int cm_run_device(mg_ctx *c, CmCall &k, const float *verts,
-                         uint32_t nverts, const uint32_t *faces,
+static int cm_run_device(mg_ctx *c, CmCall &k, uint32_t nverts,
                          uint32_t ntris, const double scale[3],
                          const double offset[3]) {
-  if (int e = cm_validate(c, verts, nverts, faces, ntris, scale, offset))
-    return e;
   k = {};
   k.nverts = nverts;
   k.ntris = ntris;
@@ -850,7 +860,7 @@ static int cm_run_device(mg_ctx *c, CmCall &k, const float *verts,
     k.g.scale[a] = scale[a];
     k.g.offset[a] = offset[a];
   }
-  if (int e = cm_count(c, k, verts, faces)) return e;
+  if (int e = cm_count(c, k)) return e;
   for (auto *b : {&c->cm_fkey, &c->cm_fkey_alt, &c->cm_fval, &c->cm_fval_alt})
     if (ensure(c, *b, (uint64_t)k.P + 1)) return 64;
   rocprim::double_buffer<uint32_t> keys(c->cm_fkey.get(),
@@ -864,12 +874,22 @@ static int cm_run_device(mg_ctx *c, CmCall &k, const float *verts,
   return cm_faces(c, k, vals.current());
 }
 
+// the same for the caller's host arrays: validation, upload, [1]..[6]
+static int cm_run_host(mg_ctx *c, CmCall &k, const float *verts,
+                       uint32_t nverts, const uint32_t *faces, uint32_t ntris,
+                       const double scale[3], const double offset[3]) {
+  if (int e = cm_validate(c, verts, nverts, faces, ntris, scale, offset))
+    return e;
+  if (int e = cm_upload(c, verts, nverts, faces, ntris)) return e;
+  return cm_run_device(c, k, nverts, ntris, scale, offset);
+}
+
 static int run_chunk_mesh(mg_ctx *c, const float *verts, uint32_t nverts,
                           const uint32_t *faces, uint32_t ntris,
                           const double scale[3], const double offset[3],
                           mg_meshset **out, const uint32_t **out_order) {
   CmCall k;
-  if (int e = cm_run_device(c, k, verts, nverts, faces, ntris, scale, offset))
+  if (int e = cm_run_host(c, k, verts, nverts, faces, ntris, scale, offset))
     return e;
   return cm_extract(c, k, out, out_order);
 }

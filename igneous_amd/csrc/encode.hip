@@ -32,6 +32,11 @@
 //   k_enc_varint_write  draco: block per label of the varint band, block
 //                       scan of the lengths chunk by chunk, bytes out
 //   k_enc_headers       thread per label: header, trailer, box as f32
+// The kernels know entries only through an EncTables (two prefix tables and
+// an offset table), so octree_level.hip drives k_enc_varint_sum, k_enc_faces,
+// k_enc_varint_write and k_enc_headers over the cells of an octree level,
+// with the integer draco layout (ENC_DRACO_INT: DT_UINT32 / sequential
+// INTEGER attribute, no trailer, no boxes) and a vertex kernel of its own.
 // Precomputed entries are multiples of 4 B at 4-aligned offsets and are
 // stored as dwords; draco entries are odd-sized and stored byte by byte —
 // no blob address is ever cast to a wider pointer there.
@@ -44,6 +49,11 @@
 // draco bytes around the data: header 11, attribute header 10, trailer 17,
 // two varints of at most 5, the connectivity byte
 #define ENC_DRACO_FIXED_MAX (11 + 5 + 5 + 1 + 10 + 17)
+// the `draco` argument of the layout and of the kernels: 0 precomputed,
+// ENC_DRACO_FLOAT the quantised f32 attribute with its 17-byte trailer,
+// ENC_DRACO_INT the integer attribute of octree_level.hip, no trailer
+#define ENC_DRACO_FLOAT 1
+#define ENC_DRACO_INT 2
 
 // final numbers of one call (the wrapper's defaulting is already applied)
 struct EncParams {
@@ -54,7 +64,8 @@ struct EncParams {
   uint32_t bits;
 };
 
-// the per-label arrays every kernel derives an entry's layout from
+// the per-entry arrays every kernel derives an entry's layout from (an
+// entry is a label here, a grid cell in octree_level.hip)
 struct EncTables {
   const uint32_t *vbase, *tri_off;  // nlabels + 1 each
   const uint64_t *ilen;             // draco: varint index bytes per label
@@ -112,7 +123,7 @@ __device__ __forceinline__ EncLayout enc_layout(const EncTables &t, int draco,
                          : e.band == ENC_BAND_U32 ? 12ull * e.nf
                                                   : t.ilen[l];
     e.vpos = e.ipos + idx + 10;
-    e.size = e.vpos + 12ull * e.nv + 17;
+    e.size = e.vpos + 12ull * e.nv + (draco == ENC_DRACO_INT ? 0 : 17);
   }
   if (e.nv == 0) e.size = 0;
   return e;
@@ -322,12 +333,12 @@ __global__ void k_enc_headers(EncTables t, EncParams p,
   const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= t.nlabels) return;
   const EncLayout e = enc_layout(t, p.draco, l);
-  float *bb = bbox + 6 * (uint64_t)l;
-  if (e.nv == 0) {
-    for (int k = 0; k < 6; ++k) bb[k] = 0.0f;
-    return;
+  if (bbox) {  // the integer layout has no boxes
+    float *bb = bbox + 6 * (uint64_t)l;
+    for (int k = 0; k < 6; ++k)
+      bb[k] = e.nv == 0 ? 0.0f : enc_unord(box[6 * (uint64_t)l + k]);
   }
-  for (int k = 0; k < 6; ++k) bb[k] = enc_unord(box[6 * (uint64_t)l + k]);
+  if (e.nv == 0) return;
   uint8_t *dst = blob + t.off[l];
   if (!p.draco) {
     *reinterpret_cast<uint32_t *>(dst) = e.nv;  // 4-aligned entry
@@ -343,9 +354,13 @@ __global__ void k_enc_headers(EncTables t, EncParams p,
   // one attributes decoder, one attribute, POSITION, DT_FLOAT32, 3
   // components, not normalised, unique id 0, sequential QUANTIZATION,
   // prediction NONE (-2), uncompressed values
-  const uint8_t attr[10] = {1, 1, 0, 9, 3, 0, 0, 2, 0xFE, 0};
+  // (ENC_DRACO_INT: DT_UINT32 and sequential INTEGER, and no trailer)
+  const bool integer = p.draco == ENC_DRACO_INT;
+  const uint8_t attr[10] = {1, 1, 0, (uint8_t)(integer ? 6 : 9), 3, 0, 0,
+                            (uint8_t)(integer ? 1 : 2), 0xFE, 0};
   uint8_t *a = dst + e.vpos - 10;
   for (int k = 0; k < 10; ++k) a[k] = attr[k];
+  if (integer) return;
   uint8_t *tr = dst + e.vpos + 12ull * e.nv;
   for (int k = 0; k < 3; ++k) enc_put_u32(tr + 4 * k, __float_as_uint(p.of[k]));
   enc_put_u32(tr + 12, __float_as_uint(p.rf));

@@ -380,35 +380,37 @@ static int mv_faces(mg_ctx *c, MvCall &k, const float *d_verts,
 }
 
 // Weld the mesh in the DEVICE arrays d_verts (V x 3) / d_faces (T x 3,
-// every index < V) and leave the result in the ctx's pinned staging. The
-// caller has validated the radius; non-finite vertices fail the range check.
-static int run_merge_close(mg_ctx *c, const float *d_verts, uint32_t V,
-                           const uint32_t *d_faces, uint32_t T, double radius,
-                           const float **out_verts, uint32_t *out_nverts,
-                           const uint32_t **out_faces, uint32_t *out_ntris) {
+// every index < V) into mv_out_v / mv_out_f; the result's counts go to
+// k.out_nverts / k.out_ntris. The caller has validated the radius;
+// non-finite vertices fail the range check.
+static int mv_run_device(mg_ctx *c, MvCall &k, const float *d_verts,
+                         uint32_t V, const uint32_t *d_faces, uint32_t T,
+                         double radius) {
+  k = {V, T, radius, 0, 0};
+  if (T == 0) return 0;  // a mesh without faces keeps no vertex
+  const uint64_t nv = V, nt = T;
+  if (ensure(c, c->mv_misc, 1)) return 101;
+  if (ensure(c, c->mv_cell, 3 * nv)) return 101;
+  for (auto *b : {&c->mv_key, &c->mv_key_alt, &c->mv_val, &c->mv_val_alt,
+                  &c->mv_parent, &c->mv_used, &c->mv_vid})
+    if (ensure(c, *b, nv + 1)) return 101;
+  for (auto *b : {&c->mv_keep, &c->mv_fslot})
+    if (ensure(c, *b, nt + 1)) return 101;
+  if (ensure(c, c->mv_out_v, 3 * nv + 3)) return 101;
+  if (ensure(c, c->mv_out_f, 3 * nt + 3)) return 101;
+  rocprim::double_buffer<uint32_t> keys(c->mv_key.get(), c->mv_key_alt.get());
+  rocprim::double_buffer<uint32_t> vals(c->mv_val.get(), c->mv_val_alt.get());
+  if (int e = mv_grid(c, k, d_verts, keys, vals)) return e;
+  if (int e = mv_link(c, k, d_verts, keys.current(), vals.current()))
+    return e;
+  return mv_faces(c, k, d_verts, d_faces);
+}
+
+// the welded mesh of mv_run_device into the ctx's pinned staging
+static int mv_download(mg_ctx *c, const MvCall &k, const float **out_verts,
+                       uint32_t *out_nverts, const uint32_t **out_faces,
+                       uint32_t *out_ntris) {
   hipStream_t s = c->stream;
-  MvCall k = {V, T, radius, 0, 0};
-  // a mesh without faces keeps no vertex
-  if (T > 0) {
-    const uint64_t nv = V, nt = T;
-    if (ensure(c, c->mv_misc, 1)) return 101;
-    if (ensure(c, c->mv_cell, 3 * nv)) return 101;
-    for (auto *b : {&c->mv_key, &c->mv_key_alt, &c->mv_val, &c->mv_val_alt,
-                    &c->mv_parent, &c->mv_used, &c->mv_vid})
-      if (ensure(c, *b, nv + 1)) return 101;
-    for (auto *b : {&c->mv_keep, &c->mv_fslot})
-      if (ensure(c, *b, nt + 1)) return 101;
-    if (ensure(c, c->mv_out_v, 3 * nv + 3)) return 101;
-    if (ensure(c, c->mv_out_f, 3 * nt + 3)) return 101;
-    rocprim::double_buffer<uint32_t> keys(c->mv_key.get(),
-                                          c->mv_key_alt.get());
-    rocprim::double_buffer<uint32_t> vals(c->mv_val.get(),
-                                          c->mv_val_alt.get());
-    if (int e = mv_grid(c, k, d_verts, keys, vals)) return e;
-    if (int e = mv_link(c, k, d_verts, keys.current(), vals.current()))
-      return e;
-    if (int e = mv_faces(c, k, d_verts, d_faces)) return e;
-  }
   const uint64_t OV = k.out_nverts, OT = k.out_ntris;
   if (ensure(c, c->h_verts, 3 * OV + 3)) return 106;
   if (ensure(c, c->h_faces, 3 * OT + 3)) return 106;
@@ -424,6 +426,15 @@ static int run_merge_close(mg_ctx *c, const float *d_verts, uint32_t V,
   *out_faces = c->h_faces.get();
   *out_ntris = (uint32_t)OT;
   return 0;
+}
+
+static int run_merge_close(mg_ctx *c, const float *d_verts, uint32_t V,
+                           const uint32_t *d_faces, uint32_t T, double radius,
+                           const float **out_verts, uint32_t *out_nverts,
+                           const uint32_t **out_faces, uint32_t *out_ntris) {
+  MvCall k;
+  if (int e = mv_run_device(c, k, d_verts, V, d_faces, T, radius)) return e;
+  return mv_download(c, k, out_verts, out_nverts, out_faces, out_ntris);
 }
 
 // mg_merge_close_vertices: host arrays in
@@ -446,22 +457,18 @@ static int run_merge_close_host(mg_ctx *c, const float *verts, uint32_t V,
                          radius, out_verts, out_nverts, out_faces, out_ntris);
 }
 
-// mg_retriangulate_mesh: the chunker's device stages, the cells gathered in
-// dict order into one mesh, then the weld. *no_cells: the chunker kept no
-// cell and nothing else was done (the caller's result is its input).
-static int run_retriangulate(mg_ctx *c, const float *verts, uint32_t nverts,
-                             const uint32_t *faces, uint32_t ntris,
-                             const double scale[3], const double offset[3],
-                             double radius, bool *no_cells,
-                             const float **out_verts, uint32_t *out_nverts,
-                             const uint32_t **out_faces,
-                             uint32_t *out_ntris) {
+// The retriangulation of the mesh in cm_verts / cm_faces, on the device: the
+// chunker's stages, the cells gathered in dict order into one mesh, then the
+// weld into mv_out_v / mv_out_f (counts in k). *no_cells: the chunker kept
+// no cell and nothing else was done (the result is the input, still in
+// cm_verts / cm_faces).
+static int mv_retriangulate_device(mg_ctx *c, MvCall &k, uint32_t nverts,
+                                   uint32_t ntris, const double scale[3],
+                                   const double offset[3], double radius,
+                                   bool *no_cells) {
   hipStream_t s = c->stream;
-  if (int e = mv_check_radius(c, radius)) return e;
   CmCall ck;
-  if (int e = cm_run_device(c, ck, verts, nverts, faces, ntris, scale,
-                            offset))
-    return e;
+  if (int e = cm_run_device(c, ck, nverts, ntris, scale, offset)) return e;
   CmCellTable t;
   if (int e = cm_read_cells(c, ck, t)) return e;
   const uint32_t n = (uint32_t)t.live.size();
@@ -493,6 +500,27 @@ static int run_retriangulate(mg_ctx *c, const float *verts, uint32_t nverts,
                      c->mv_verts.get(), c->mv_faces.get());
   HIP_TRY(c, hipGetLastError(), 107);
   HIP_TRY(c, hipStreamSynchronize(s), 107);  // tab is read: it may go
-  return run_merge_close(c, c->mv_verts.get(), dv, c->mv_faces.get(), df,
-                         radius, out_verts, out_nverts, out_faces, out_ntris);
+  return mv_run_device(c, k, c->mv_verts.get(), dv, c->mv_faces.get(), df,
+                       radius);
+}
+
+// mg_retriangulate_mesh: host arrays in, the welded mesh downloaded. With
+// *no_cells set nothing is downloaded (the caller's result is its input).
+static int run_retriangulate(mg_ctx *c, const float *verts, uint32_t nverts,
+                             const uint32_t *faces, uint32_t ntris,
+                             const double scale[3], const double offset[3],
+                             double radius, bool *no_cells,
+                             const float **out_verts, uint32_t *out_nverts,
+                             const uint32_t **out_faces,
+                             uint32_t *out_ntris) {
+  if (int e = mv_check_radius(c, radius)) return e;
+  if (int e = cm_validate(c, verts, nverts, faces, ntris, scale, offset))
+    return e;
+  if (int e = cm_upload(c, verts, nverts, faces, ntris)) return e;
+  MvCall k;
+  if (int e = mv_retriangulate_device(c, k, nverts, ntris, scale, offset,
+                                      radius, no_cells))
+    return e;
+  if (*no_cells) return 0;
+  return mv_download(c, k, out_verts, out_nverts, out_faces, out_ntris);
 }

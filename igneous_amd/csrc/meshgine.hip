@@ -1582,6 +1582,7 @@ static int check_label_map(mg_ctx *c, const mg_label_map *map, int dtype,
 
 #include "chunk_mesh.hip"
 #include "merge_verts.hip"
+#include "octree_level.hip"
 #include "count_voxels.hip"
 
 // MG_FLAG_COUNTED: the resident volume must be the one the mg_count_voxels
@@ -1933,5 +1934,31 @@ int mg_retriangulate_mesh(mg_ctx *c,
   }
   return 0;
 }
+
+// Encode one level of one mesh's multires octree (see meshgine.h). The
+// pipeline is in octree_level.hip.
+int mg_encode_octree_level(mg_ctx *c,
+                           const float *verts, uint32_t nverts,
+                           const uint32_t *faces, uint32_t ntris,
+                           const mg_octree_level *lv, mg_fragset **out) {
+  if (!c) { SET_ERR(c, "null ctx"); return 1; }
+  std::lock_guard<std::mutex> g(c->lock);
+  c->err.clear();
+  if (!lv || !out || (nverts > 0 && !verts) || (ntris > 0 && !faces)) {
+    SET_ERR(c, "null argument");
+    return 1;
+  }
+  *out = nullptr;
+  c->counted_valid = false;  // a stash belongs to the call just before
+  if (ntris > (1u << 31) / 3 || nverts > (1u << 31)) {
+    SET_ERR(c, "mesh too large (%u vertices, %u tris)", nverts, ntris);
+    return 2;
+  }
+  HIP_TRY(c, hipSetDevice(c->device), 4);
+  return run_octree_level(c, verts, nverts, faces, ntris, lv, out);
+}
+
+// the blob is ctx-owned (pinned, reused); this frees the descriptor
+void mg_fragset_free(mg_fragset *fs) { free(fs); }
 
 }  // extern "C"

@@ -155,6 +155,12 @@ struct DeviceBuffers {
   DevArr<uint32_t> enc_box;
   DevArr<float> enc_bbox;
   DevArr<uint8_t> enc_blob;
+  // octree level (octree_level.hip), beside the enc_* arrays it reuses: the
+  // entries in z-order, each entry's node, the z-ordered sizes and offsets,
+  // the two-entry prefix tables of the unchunked level
+  DevArr<uint32_t> ol_order, ol_pref;
+  DevArr<int32_t> ol_node;
+  DevArr<uint64_t> ol_zsize, ol_zoff;
 };
 
 // Timing / ordering events of one mesh_chunk_impl call. EV_H2D_END is

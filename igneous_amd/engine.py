@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -42,6 +42,7 @@ _EXPORTED_SYMBOLS = [
     "mg_mesh_chunk_encoded", "mg_blobset_free",
     "mg_count_voxels", "mg_label_counts_free",
     "mg_merge_close_vertices", "mg_retriangulate_mesh",
+    "mg_encode_octree_level", "mg_fragset_free",
 ]
 MG_ENC_PRECOMPUTED, MG_ENC_DRACO = 0, 1
 
@@ -145,6 +146,68 @@ class _MgBlobSet(ctypes.Structure):
         ("blob", ctypes.POINTER(ctypes.c_uint8)),
         ("blob_bytes", ctypes.c_uint64),
     ]
+
+
+# mg_octree_level.order_cells: (nodes[3n] in dict order, n, order[n], arg)
+_ORDER_CELLS_FN = ctypes.CFUNCTYPE(
+    ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32,
+    ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p)
+
+
+class _MgOctreeLevel(ctypes.Structure):
+    _fields_ = [
+        ("scale", ctypes.c_double * 3),
+        ("offset", ctypes.c_double * 3),
+        ("retriangulate", ctypes.c_uint32),
+        ("upper_scale", ctypes.c_double * 3),
+        ("radius", ctypes.c_double),
+        ("chunked", ctypes.c_uint32),
+        ("q_origin", ctypes.c_double * 3),
+        ("q_voffset", ctypes.c_double * 3),
+        ("q_cell", ctypes.c_double * 3),
+        ("q_bits", ctypes.c_uint32),
+        ("order_cells", _ORDER_CELLS_FN),
+        ("order_arg", ctypes.c_void_p),
+    ]
+
+
+class _MgFragSet(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint32),
+        ("nodes", ctypes.POINTER(ctypes.c_int32)),
+        ("offset", ctypes.POINTER(ctypes.c_uint64)),
+        ("size", ctypes.POINTER(ctypes.c_uint64)),
+        ("nverts", ctypes.POINTER(ctypes.c_uint32)),
+        ("ntris", ctypes.POINTER(ctypes.c_uint32)),
+        ("blob", ctypes.POINTER(ctypes.c_uint8)),
+        ("blob_bytes", ctypes.c_uint64),
+    ]
+
+
+class EncodedLevel(NamedTuple):
+    """The finished fragments of one octree level (mg_fragset), in z-order:
+    each fragment's node, its byte size, and the fragments back to back."""
+    nodes: tuple
+    sizes: list
+    blob: bytes
+
+
+@_ORDER_CELLS_FN
+def _order_cells(nodes, n, order, _arg):
+    """mg_octree_level.order_cells: the host sequence's own sort, for grids
+    with cells of both signs on one axis, where cmp_zorder is no total order
+    and only the same sort of the same sequence gives the same result."""
+    try:
+        import functools
+        from .tasks.multires import cmp_zorder
+        keys = [tuple(nodes[3 * i:3 * i + 3]) for i in range(n)]
+        ranked = sorted(range(n), key=functools.cmp_to_key(
+            lambda a, b: cmp_zorder(keys[a], keys[b])))
+        for r, i in enumerate(ranked):
+            order[r] = i
+        return 0
+    except Exception:  # an exception cannot cross the C frame
+        return 1
 
 
 class _MgLabelCounts(ctypes.Structure):
@@ -363,6 +426,15 @@ def load_library() -> ctypes.CDLL:
             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
             ctypes.c_double,
         ] + mesh_out
+        lib.mg_encode_octree_level.restype = ctypes.c_int
+        lib.mg_encode_octree_level.argtypes = [
+            ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.c_void_p, ctypes.c_uint32,
+            ctypes.POINTER(_MgOctreeLevel),
+            ctypes.POINTER(ctypes.POINTER(_MgFragSet)),
+        ]
+        lib.mg_fragset_free.argtypes = [ctypes.POINTER(_MgFragSet)]
         _lib = lib
         return lib
 
@@ -876,6 +948,63 @@ class Engine:
         return self._weld_call("mg_retriangulate_mesh", verts, faces, radius,
                                scale, offset)
 
+    def encode_octree_level(self, verts: np.ndarray, faces: np.ndarray, *,
+                            scale, offset, upper_scale=None,
+                            radius: float = 1e-5, chunked: bool = True,
+                            q_origin, q_voffset, q_cell,
+                            q_bits: int) -> EncodedLevel:
+        """One level of a mesh's multires octree, from the mesh to the
+        finished fragment bytes, in one device call
+        (mg_encode_octree_level; create_octree_level_from_mesh of
+        multires.py:556-585 and the quantise + draco loop of :152-174,
+        byte-equal to tasks.multires.encode_octree_level_host).
+          scale, offset   this level's grid (chunk_shape * 2^lod, grid_origin)
+          upper_scale     not None (lod > 0): retriangulate at that grid first
+          chunked         False for the coarsest level: one fragment at
+                          (0, 0, 0)
+          q_*             to_stored_model_space's numbers; q_cell is the f64
+                          product chunk_shape * lod_scale
+        The mesh stays on the device between the stages; only the tables
+        and the blob come back."""
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1, 3)
+        vec = ctypes.c_double * 3
+        lv = _MgOctreeLevel()
+        lv.scale = vec(*[float(x) for x in scale])
+        lv.offset = vec(*[float(x) for x in offset])
+        lv.retriangulate = 0 if upper_scale is None else 1
+        lv.upper_scale = vec(*[float(x) for x in (
+            scale if upper_scale is None else upper_scale)])
+        lv.radius = float(radius)
+        lv.chunked = 1 if chunked else 0
+        lv.q_origin = vec(*[float(x) for x in q_origin])
+        lv.q_voffset = vec(*[float(x) for x in q_voffset])
+        lv.q_cell = vec(*[float(x) for x in q_cell])
+        q_bits = int(q_bits)
+        # out of c_uint32's range is out of 1..32 all the same
+        lv.q_bits = q_bits if 0 <= q_bits < 2 ** 32 else 0
+        lv.order_cells = _order_cells
+        out = ctypes.POINTER(_MgFragSet)()
+        # the blob is a view of the ctx's pinned staging: hold the lock
+        # until it is copied
+        with self._lock:
+            rc = self.lib.mg_encode_octree_level(
+                self.ctx,
+                v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
+                f.ctypes.data_as(ctypes.c_void_p), f.shape[0],
+                ctypes.byref(lv), ctypes.byref(out))
+            self._check(rc, "mg_encode_octree_level")
+            try:
+                fs = out.contents
+                n = int(fs.n)
+                nodes = _np_array(fs.nodes, 3 * n).reshape(n, 3).tolist()
+                sizes = _np_array(fs.size, n).tolist()
+                nbytes = int(fs.blob_bytes)
+                blob = ctypes.string_at(fs.blob, nbytes) if nbytes else b""
+            finally:
+                self.lib.mg_fragset_free(out)
+        return EncodedLevel(tuple(tuple(p) for p in nodes), sizes, blob)
+
     def stats(self) -> dict:
         s = MgStatsEncode()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
@@ -988,6 +1117,19 @@ def retriangulate_mesh(mesh, scale, offset, radius: float = 1e-5,
     v, f = _engine(device_id).retriangulate_mesh(
         mesh.vertices, mesh.faces, scale, offset, radius)
     return Mesh(v, f, id=mesh.id)
+
+
+def encode_octree_level(mesh, *, scale, offset, upper_scale=None,
+                        radius: float = 1e-5, chunked: bool = True,
+                        q_origin, q_voffset, q_cell, q_bits: int,
+                        device_id: Optional[int] = None) -> EncodedLevel:
+    """Module-level octree level encoder: Mesh -> EncodedLevel; see
+    Engine.encode_octree_level."""
+    return _engine(device_id).encode_octree_level(
+        mesh.vertices, mesh.faces, scale=scale, offset=offset,
+        upper_scale=upper_scale, radius=radius, chunked=chunked,
+        q_origin=q_origin, q_voffset=q_voffset, q_cell=q_cell,
+        q_bits=q_bits)
 
 
 def simplify_mesh(mesh, target_count: int, max_error: float = 1e30,

@@ -20,6 +20,10 @@ specs/algorithms — DESIGN.md §7):
                                           -> the HIP engine's
         retriangulate_mesh via the `set_retriangulator` seam (the host
         composition over igneous_amd.meshops is the bit-equal CPU checker)
+  one whole LOD (create_octree_level_from_mesh + the quantise and draco
+  loop of process_mesh)                   -> encode_octree_level_host, the
+        shared per-level function, or the HIP engine's encode_octree_level
+        (one device call, byte-equal) via the `set_level_encoder` seam
   zmesh.simplify_fqmr                     -> the HIP quadric simplifier
         via the `set_simplifier` seam (default: engine.simplify_mesh on
         the GPU; the pyfqmr aggressiveness/K error schedule is NOT
@@ -62,6 +66,9 @@ __all__ = [
     "set_simplifier",
     "set_chunker",
     "set_retriangulator",
+    "set_level_encoder",
+    "encode_octree_level_host",
+    "engine_level_encoder",
 ]
 
 # ---------------------------------------------------------------------------
@@ -148,6 +155,66 @@ def _get_retriangulator():
     def gpu_retriangulate(mesh: Mesh, scale, offset) -> Mesh:
         return engine.retriangulate_mesh(mesh, scale, offset, radius=1e-5)
     return gpu_retriangulate
+
+
+# Level encoder seam, beside the three above and under the same rule: an
+# injected encoder wins; with an injected simplifier, chunker or
+# retriangulator the host sequence runs (encode_octree_level_host, which
+# goes through the seams above); otherwise the default below decides.
+# fn(mesh, chunk_shape, lod, num_lods, grid_origin, vertex_quantization_bits,
+#    draco_compression_level) -> (nodes, sizes, blob): the level's fragment
+# positions in z-order, each fragment's byte size, the fragments joined.
+
+_level_encoder_fn = None
+
+# Whether the engine's one-call encoder is the default of the product path.
+# The rule of DESIGN.md §4 ("Device encode") decides it: the device call is
+# the default only if it beats the host sequence by more than three times
+# the host sequence's own max-min on EVERY row of
+# tools/probe_octree_level.py. It won every row and its bytes were equal on
+# every row, but two of the five rows missed the margin (DESIGN.md §4
+# "Device octree level": 6016 faces in 8 cells, 0.317 ms gained, 0.342 ms
+# asked; the unchunked row, 0.262 ms gained, 0.633 ms asked), so the host
+# sequence stays the default until a probe says otherwise. The call itself
+# is complete: set this to True, or set_level_encoder(engine_level_encoder),
+# to hand the levels over.
+DEVICE_LEVEL_ENCODER_DEFAULT = False
+
+
+def set_level_encoder(fn) -> None:
+    """Test seam. Pass None to restore the default selection."""
+    global _level_encoder_fn
+    _level_encoder_fn = fn
+
+
+def engine_level_encoder(mesh: Mesh, chunk_shape, lod: int, num_lods: int,
+                         grid_origin, vertex_quantization_bits: int,
+                         draco_compression_level: int = 7):
+    """One octree level in one engine call (engine.encode_octree_level):
+    the mesh stays on the device from the retriangulation to the encoded
+    bytes. No CPU fallback: an engine error raises."""
+    from .. import engine
+    chunk = np.asarray(chunk_shape, dtype=np.float64)
+    level = engine.encode_octree_level(
+        mesh,
+        scale=chunk * (2 ** lod), offset=grid_origin,
+        upper_scale=chunk * (2 ** (lod - 1)) if lod > 0 else None,
+        radius=1e-5, chunked=lod != num_lods - 1,
+        q_origin=grid_origin, q_voffset=(0, 0, 0),
+        q_cell=chunk * float(2 ** lod),
+        q_bits=vertex_quantization_bits)
+    return level.nodes, level.sizes, level.blob
+
+
+def _get_level_encoder():
+    if _level_encoder_fn is not None:
+        return _level_encoder_fn
+    if (_simplifier_fn is not None or _chunker_fn is not None
+            or _retriangulator_fn is not None):
+        return encode_octree_level_host
+    if DEVICE_LEVEL_ENCODER_DEFAULT:
+        return engine_level_encoder
+    return encode_octree_level_host
 
 
 # ---------------------------------------------------------------------------
@@ -237,6 +304,53 @@ def create_octree_level_from_mesh(mesh: Mesh, chunk_shape, lod: int,
     return (list(submeshes), nodes)
 
 
+def encode_octree_level_host(mesh: Mesh, chunk_shape, lod: int,
+                             num_lods: int, grid_origin,
+                             vertex_quantization_bits: int,
+                             draco_compression_level: int = 7):
+    """One LOD of process_mesh on the host (multires.py:556-585 and
+    :152-174): create_octree_level_from_mesh, then to_stored_model_space and
+    the draco encode per fragment. -> (nodes, sizes, blob). This is the
+    contract the engine's encode_octree_level is byte-equal to."""
+    submeshes, nodes = create_octree_level_from_mesh(
+        mesh, chunk_shape, lod, num_lods, grid_origin, None)
+    vqb = int(vertex_quantization_bits)
+    # to_stored_model_space reads the level's numbers off a manifest
+    manifest = MultiLevelPrecomputedMeshManifest(
+        segment_id=mesh.id,
+        chunk_shape=chunk_shape,
+        grid_origin=grid_origin,
+        num_lods=num_lods,
+        lod_scales=[2 ** i for i in range(num_lods)],
+        vertex_offsets=[[0, 0, 0]] * num_lods,
+        num_fragments_per_lod=[len(submeshes) if i == lod else 0
+                               for i in range(num_lods)],
+        fragment_positions=[nodes if i == lod else ()
+                            for i in range(num_lods)],
+    )
+    sizes = []
+    mesh_binaries = []
+    for frag_no, submesh in enumerate(submeshes):
+        if len(submesh.faces) == 0:
+            sizes.append(0)
+            mesh_binaries.append(b"")
+            continue
+        stored = to_stored_model_space(
+            submesh.vertices, manifest, lod=lod,
+            vertex_quantization_bits=vqb, frag=frag_no)
+        try:
+            binary = draco_fmt.encode(
+                stored, submesh.faces,
+                quantization_bits=vqb,
+                compression_level=draco_compression_level,
+            )
+        except draco_fmt.EncodingFailedException:
+            binary = b""
+        sizes.append(len(binary))
+        mesh_binaries.append(binary)
+    return tuple(nodes), sizes, b"".join(mesh_binaries)
+
+
 def process_mesh(vol: PrecomputedVolume,
                  mesh_info: dict,
                  label: int,
@@ -271,14 +385,13 @@ def process_mesh(vol: PrecomputedVolume,
     if np.any(chunk_shape == 0):
         return (None, None)
 
-    lods = [
-        create_octree_level_from_mesh(
-            lods[lod], chunk_shape, lod, len(lods), grid_origin,
-            mesh_shape)
+    vqb = int(mesh_info["vertex_quantization_bits"])
+    encode_level = _get_level_encoder()
+    levels = [
+        encode_level(lods[lod], chunk_shape, lod, len(lods), grid_origin,
+                     vqb, draco_compression_level)
         for lod in range(len(lods))
     ]
-    fragment_positions = [nodes for submeshes, nodes in lods]
-    lods = [submeshes for submeshes, nodes in lods]
 
     manifest = MultiLevelPrecomputedMeshManifest(
         segment_id=label,
@@ -287,35 +400,12 @@ def process_mesh(vol: PrecomputedVolume,
         num_lods=len(lods),
         lod_scales=[2 ** i for i in range(len(lods))],
         vertex_offsets=[[0, 0, 0]] * len(lods),
-        num_fragments_per_lod=[len(lods[lod]) for lod in range(len(lods))],
-        fragment_positions=fragment_positions,
-        fragment_offsets=[],
+        num_fragments_per_lod=[len(nodes) for nodes, _, _ in levels],
+        fragment_positions=[nodes for nodes, _, _ in levels],
+        fragment_offsets=[int(size) for _, sizes, _ in levels
+                          for size in sizes],
     )
-
-    vqb = int(mesh_info["vertex_quantization_bits"])
-
-    mesh_binaries = []
-    for lod, submeshes in enumerate(lods):
-        for frag_no, submesh in enumerate(submeshes):
-            if len(submesh.faces) == 0:
-                manifest.fragment_offsets.append(0)
-                mesh_binaries.append(b"")
-                continue
-            stored = to_stored_model_space(
-                submesh.vertices, manifest, lod=lod,
-                vertex_quantization_bits=vqb, frag=frag_no)
-            try:
-                binary = draco_fmt.encode(
-                    stored, submesh.faces,
-                    quantization_bits=vqb,
-                    compression_level=draco_compression_level,
-                )
-            except draco_fmt.EncodingFailedException:
-                binary = b""
-            manifest.fragment_offsets.append(len(binary))
-            mesh_binaries.append(binary)
-
-    return (manifest, b"".join(mesh_binaries))
+    return (manifest, b"".join(blob for _, _, blob in levels))
 
 
 # ---------------------------------------------------------------------------

@@ -46,6 +46,11 @@
  *   mg_retriangulate_mesh — replaces retriangulate_mesh as a whole
  *                        (multires.py:546-553): chunk, concatenate and weld
  *                        without the cells leaving the device.
+ *   mg_encode_octree_level — replaces, for one lod of the multires merge,
+ *                        create_octree_level_from_mesh (multires.py:556-585)
+ *                        and the to_stored_model_space + DracoPy.encode loop
+ *                        (multires.py:152-174): the mesh is uploaded once
+ *                        and the level's finished fragment bytes come back.
  *   mg_mesh_chunk_encoded — mg_mesh_chunk_mapped plus the per-label loop
  *                        that follows it in MeshTask: the shift into
  *                        global nm (mesh.py:434-435), the spatial-index
@@ -490,6 +495,91 @@ int mg_retriangulate_mesh(mg_ctx *ctx,
                           double radius,
                           const float **out_verts, uint32_t *out_nverts,
                           const uint32_t **out_faces, uint32_t *out_ntris);
+
+/* One level of one mesh's multires octree: where it is cut and how its
+ * fragments are quantised (the arguments of the reference's
+ * igneous/tasks/mesh/multires.py:556-585 create_octree_level_from_mesh and
+ * of the to_stored_model_space + DracoPy.encode loop at :152-174). */
+typedef struct mg_octree_level {
+  double   scale[3];        /* cell size of this level: chunk_shape * 2^lod */
+  double   offset[3];       /* grid anchor (the manifest's grid_origin) */
+  uint32_t retriangulate;   /* lod > 0: first cut at upper_scale and weld */
+  double   upper_scale[3];  /* cell size of the level below: scale / 2 */
+  double   radius;          /* the weld's radius (the reference's 1e-5) */
+  uint32_t chunked;         /* 0: the coarsest level, one fragment at (0,0,0) */
+  double   q_origin[3];     /* grid_origin */
+  double   q_voffset[3];    /* the level's vertex_offsets entry */
+  double   q_cell[3];       /* chunk_shape * lod_scale, as one f64 product */
+  uint32_t q_bits;          /* vertex_quantization_bits, 1..32 */
+  /* Optional. cmp_zorder is a total order only while no axis holds cells of
+   * both signs; where one does, the result of a comparison sort depends on
+   * the sort's algorithm and on the order it is handed the cells in. The
+   * engine then calls order_cells with the n cells (3 i32 each) in
+   * mg_chunk_mesh's dict order, and it stores in order[r] the index of the
+   * cell that comes r-th; a non-zero return fails the call. NULL, and
+   * wherever cmp_zorder is a total order: the engine's own sort by the
+   * z-order of the coordinates biased by 2^20, which is cmp_zorder's order
+   * there. Grids anchored at the mesh's minimum, as the merge anchors them,
+   * have no negative cell and never reach the callback. */
+  int (*order_cells)(const int32_t *nodes, uint32_t n, uint32_t *order,
+                     void *arg);
+  void    *order_arg;
+} mg_octree_level;
+
+/* The finished fragments of one octree level, in z-order. The tables live in
+ * the descriptor allocation (mg_fragset_free); the blob is ctx-owned pinned
+ * staging under the mg_simplify_mesh lifetime rule. */
+typedef struct mg_fragset {
+  uint32_t  n;
+  int32_t  *nodes;       /* [3n] fragment_positions of the level */
+  uint64_t *offset;      /* [n] start of the fragment in blob */
+  uint64_t *size;        /* [n] bytes: the level's fragment_offsets slice */
+  uint32_t *nverts;      /* [n] */
+  uint32_t *ntris;       /* [n] */
+  const uint8_t *blob;   /* b"".join(mesh_binaries) of the level */
+  uint64_t  blob_bytes;
+} mg_fragset;
+
+/* Encode ONE level of one mesh's multires octree on the device — replaces,
+ * for one lod, create_octree_level_from_mesh (the reference's
+ * igneous/tasks/mesh/multires.py:556-585: retriangulate_mesh,
+ * zmesh.chunk_mesh, the cmp_zorder sort) and the per-fragment
+ * to_stored_model_space + DracoPy.encode loop of process_mesh (:152-174).
+ * The mesh is uploaded once and stays on the device between the
+ * retriangulation, the chunker and the encode; only the tables and the blob
+ * come back. Byte-equal to the host sequence (contract in DESIGN.md §7a):
+ *   1. lv->retriangulate: M <- mg_retriangulate_mesh(M, upper_scale, offset,
+ *      radius); M stays when the chunker keeps no cell
+ *   2. lv->chunked == 0: one fragment, M itself, at node (0, 0, 0);
+ *      otherwise the cells of mg_chunk_mesh(M, scale, offset) sorted by
+ *      cmp_zorder on (cx, cy, cz)
+ *   3. per fragment with node p, in f64, one IEEE operation per step:
+ *      clip(rint(((((v - q_origin) - q_voffset) / q_cell) - p) * qmax),
+ *      0, qmax) as u32, qmax = 2^q_bits - 1
+ *   4. per fragment the draco bytes of integer positions: 11-byte header,
+ *      varint nf, varint nv, u8 1, indices at u8 / u16 / varint / u32 by
+ *      nv < 2^8 / 2^16 / 2^21 / else, the 10-byte attribute header
+ *      (DT_UINT32, sequential INTEGER, prediction -2, uncompressed), 3*nv
+ *      u32 — no trailer. A fragment without faces (the unchunked fragment of
+ *      a mesh without faces) has size 0.
+ *   5. the fragments lie in blob in z-order, back to back from offset 0
+ * An empty chunked level gives n == 0. Return codes (non-zero return +
+ * mg_last_error, never a fault, the ctx stays usable):
+ *   110  rejected before any kernel: q_bits outside 1..32, a non-finite
+ *        q_origin / q_voffset / q_cell, a q_cell component <= 0
+ *   111  device allocation or a table upload failed
+ *   112  the order_cells callback failed or returned no permutation
+ *   113  the encode kernels or the size scan failed
+ *   114  the download failed       115  out of host memory
+ * besides 1, 2 and 4 as above, mg_chunk_mesh's (60-73: 60 also rejects, before
+ * any kernel, a face index >= nverts and a non-finite vertex, scale,
+ * upper_scale or offset) and mg_merge_close_vertices' (100-107). */
+int mg_encode_octree_level(mg_ctx *ctx,
+                           const float *verts, uint32_t nverts,
+                           const uint32_t *faces, uint32_t ntris,
+                           const mg_octree_level *lv, mg_fragset **out);
+
+void mg_fragset_free(mg_fragset *fs);
 
 /* Stats of the last mg_mesh_chunk on this ctx. Returns 0 on success. */
 int mg_get_stats(mg_ctx *ctx, mg_stats *out);

@@ -29,14 +29,17 @@
 //                      record + 4-B label id per ITEM in canonical
 //                      global order
 //   [4] partition      rocPRIM stable radix-sort of the items by label
-//                      id; scan of the sorted items' triangle counts
-//                      -> itoff; per-label triangle ranges
+//                      id; one u64 scan of the sorted items' vertex and
+//                      triangle counts -> itscan (every item's first
+//                      vertex id and first triangle); per-label triangle,
+//                      item and vertex ranges
 //   [5] weld           expand items into triangles (t ascending within
 //                      an item: the per-triangle stream, label by label
-//                      in emit order); direct-addressed (edge,side)
-//                      table of first positions, bit-packed
-//                      first-occurrence flags + word-granular scan ->
-//                      vertex ids, vertex emit, per-label face indices
+//                      in emit order); first corners take their ids from
+//                      itscan and write the vertices, later corners look
+//                      their slot up: one workgroup per label with the
+//                      (slot -> id) table in LDS, a direct-addressed
+//                      global table for labels above WELD_LDS_CAP vertices
 //   [6] (optional) per-label quadric simplification (one workgroup per
 //                      label; global matched-pair rounds for huge labels)
 //   [7] D2H slices + meshset assembly (ctx-owned pinned staging)
@@ -45,8 +48,9 @@
 //       D2H of the blob and the per-label tables
 //
 // Determinism: every kernel's output is a pure function of its inputs —
-// atomics are only used for first-position minima (order-free), hash slot
-// claims (value-keyed) and the label counter (affects internal ids only;
+// atomics are only used for hash slot claims (value-keyed; the place of an
+// entry in a table never reaches the output), the weld's block list (its
+// order is free) and the label counter (affects internal ids only;
 // triangle partition order is by internal id but per-label content and the
 // final label-sorted meshset are invariant).
 
@@ -54,6 +58,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #define MC_TABLE_QUAL __device__ static const
@@ -542,67 +547,82 @@ __global__ __launch_bounds__(256, 8) void k_emit(
   }
 }
 
-// [4b] triangles of one item, the input of the scan that gives itoff
-// (item -> first triangle of the label-partitioned stream): through the
-// sorted records themselves, or through the sort's permutation
-struct ItemTris {
-  __device__ uint32_t operator()(uint2 rec) const {
-    return MC_TRI_COUNT[rec.y & 255u];
+// [4b] the two counts of one item as one u64, (vertices << 32) | triangles,
+// the input of the item scan (the k_count / segcnt pattern: both totals stay
+// below 2^32, so the halves never carry into each other). The vertices of an
+// item are its first-occurrence corners (MC_ITEM_FIRST, see "welding"
+// below). Read through the sorted records themselves, or through the sort's
+// permutation.
+__device__ __forceinline__ uint32_t item_first_bits(uint2 rec) {
+  // interior = the axes on which the cell's coordinate is above 0
+  return MC_ITEM_FIRST[rec.y & 255u][~(rec.y >> 11) & 7u];
+}
+struct ItemCounts {
+  __device__ uint64_t operator()(uint2 rec) const {
+    return ((uint64_t)__popc(item_first_bits(rec)) << 32) |
+           MC_TRI_COUNT[rec.y & 255u];
   }
 };
-struct ItemTrisVia {
+struct ItemCountsVia {
   const uint2 *recs;
-  __device__ uint32_t operator()(uint32_t o) const {
-    return MC_TRI_COUNT[recs[o].y & 255u];
+  __device__ uint64_t operator()(uint32_t o) const {
+    return ItemCounts{}(recs[o]);
   }
 };
 
-// [4c] one thread per sorted ITEM i, which holds triangles
-// [itoff[i], itoff[i+1]) of the stream. itoff[1..nitems] is the inclusive
-// scan of the items' triangle counts; itoff[0] = 0 is stored here.
-//  - per-label triangle ranges (labels sorted, every id present): where
-//    the label changes, tri_off[label] = the item's first triangle
-//  - blk_item[b] = the item that holds triangle b * WELD_FIRST_BLK, the
-//    first item of k_weld_first's block b. An item has at most MC_MAX_TRIS
-//    < WELD_FIRST_BLK triangles, so it holds at most one such triangle,
-//    and every b below ceil(ntris / WELD_FIRST_BLK) is held by some item.
-#define WELD_FIRST_BLK 256
+// [4c] one thread per sorted ITEM i. itscan[1..nitems] is the inclusive scan
+// of the items' counts, itscan[0] = 0 is stored here: the low half of
+// itscan[i] is item i's first triangle of the stream, the high half its first
+// global vertex id.
+//  - per label (labels sorted, every id present), where the label changes:
+//    tri_off[label] = the item's first triangle, lab_item[label] = the item,
+//    vbase[label] = the item's first vertex. Entry nlabels of each holds the
+//    total.
+//  - blk_item[b] = the item that holds triangle b * WELD_BLK, the first item
+//    of k_weld_first's block b. An item has at most MC_MAX_TRIS < WELD_BLK
+//    triangles, so it holds at most one such triangle, and every b below
+//    ceil(ntris / WELD_BLK) is held by some item.
+#define WELD_BLK 256
 __global__ void k_label_ranges(const uint32_t *__restrict__ item_lab,
-                               uint32_t *__restrict__ itoff,
+                               uint64_t *__restrict__ itscan,
                                uint32_t *__restrict__ tri_off,
+                               uint32_t *__restrict__ lab_item,
+                               uint32_t *__restrict__ vbase,
                                uint32_t *__restrict__ blk_item,
-                               uint64_t nitems, uint64_t ntris,
-                               uint32_t nlabels) {
+                               uint64_t nitems, uint32_t nlabels) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nitems) return;
-  uint32_t a = 0;
+  uint64_t sa = 0;
   if (i == 0) {
-    itoff[0] = 0;
-    tri_off[item_lab[0]] = 0;  // first label's range starts at 0
-    tri_off[nlabels] = (uint32_t)ntris;
+    itscan[0] = 0;
+    const uint64_t tot = itscan[nitems];
+    tri_off[nlabels] = (uint32_t)tot;
+    vbase[nlabels] = (uint32_t)(tot >> 32);
+    lab_item[nlabels] = (uint32_t)nitems;
   } else {
-    a = itoff[i];
-    if (item_lab[i] != item_lab[i - 1]) tri_off[item_lab[i]] = a;
+    sa = itscan[i];
   }
-  const uint32_t b = itoff[i + 1];
+  const uint32_t a = (uint32_t)sa;
+  if (i == 0 || item_lab[i] != item_lab[i - 1]) {
+    const uint32_t l = item_lab[i];
+    tri_off[l] = a;
+    lab_item[l] = (uint32_t)i;
+    vbase[l] = (uint32_t)(sa >> 32);
+  }
+  const uint32_t b = (uint32_t)itscan[i + 1];
   // the first block boundary at or after a
-  const uint32_t m = (a + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK;
-  if (m * WELD_FIRST_BLK < b) blk_item[m] = (uint32_t)i;
+  const uint32_t m = (a + WELD_BLK - 1) / WELD_BLK;
+  if (m * WELD_BLK < b) blk_item[m] = (uint32_t)i;
 }
 
 // ---------------------------------------------------------------------------
 // welding
-
-// Direct-addressed weld table: an edge midpoint is a vertex only for the
-// labels of the edge's two endpoint voxels, so (edge, side) is a
-// collision-free address — no hash, no probing, and label-partitioned
-// corner streams touch CONTIGUOUS table lines (the reference's spatial
-// locality survives). wminp[slot] holds the slot's first stream position.
 //
-// slot = axis*nvox + linear_voxel(vx,vy,vz), doubled; axis = the key's
-// odd coordinate. Capacity bound: 6*nvox must fit in u32 (checked on the
-// host; matches the reference's own 32-bit mesher task bound,
-// igneous_cli/cli.py:1049-1052).
+// A weld slot names one possible vertex: an edge midpoint is a vertex only
+// for the labels of the edge's two endpoint voxels, so (edge, side) is a
+// collision-free name. slot = ((linear_voxel * 3 + axis) << 1) | side, below
+// 6 * nvox, which must fit in u32 (checked on the host; matches the
+// reference's own 32-bit mesher task bound, igneous_cli/cli.py:1049-1052).
 //
 // Whether a corner is the first occurrence of its slot in its label's
 // stream is a function of its record alone. The partition is stable, so
@@ -614,210 +634,351 @@ __global__ void k_label_ranges(const uint32_t *__restrict__ item_lab,
 // occurrence sits in the lowest cell holding the edge — on each axis b
 // perpendicular to the edge, either the edge is on the cell's upper side
 // or c_b == 0 (MC_EDGE_NEED against the record's boundary bits) — at the
-// mask's first (t, v) using the edge (MC_TRI_FIRST).
+// mask's first (t, v) using the edge (MC_TRI_FIRST). MC_ITEM_FIRST holds
+// that predicate per item, bit 3t + v.
+//
+// Vertices are numbered in first-occurrence order of the stream. The item
+// scan gives every item its first vertex id, so a first corner's id is
+// itscan[item] >> 32 plus its rank among the item's first corners, and a
+// label's ids start at vbase[label]. What is left for the weld is the id of
+// every LATER corner: the id its slot's first corner got. That first corner
+// always lies earlier in the same label's stream, so a table of (slot -> id)
+// per label answers it:
+//  - k_weld_label keeps the table in LDS, one workgroup per label, for
+//    labels of at most WELD_LDS_CAP vertices;
+//  - larger labels go through a direct-addressed table in global memory
+//    (wminp, one u32 per slot): k_weld_plan lists the 256-triangle blocks of
+//    the stream that hold their triangles, k_weld_first and k_weld_faces
+//    run over that list alone.
 
-// [5a] one thread per TRIANGLE of the label-partitioned stream: decode
-// the three slots, write the slot triple, and for each first-occurrence
-// corner store its stream position into wminp with a plain store (one
-// writer per slot). The table is never cleared: every slot the fused
-// kernel reads was stored here, in this call, by its unique first corner.
-//
-// Flags leave as a bit array, one u64 word per 64 consecutive corners
-// (vertex ids come from a word-granular scan + popcount). A wave's 64
-// triangles are corners [192w, 192w+192) = words 3w..3w+2: three ballots,
-// one per v, re-interleaved into corner order by a second ballot per word.
-//
-// The stream arrives per ITEM (k_emit): the block expands its items into
-// triangles. Its 256 consecutive triangles lie in at most 256 consecutive
-// items, since every item has at least one triangle; the first of them is
-// blk_item[block] (k_label_ranges). Thread i takes item first + i: it
-// stages the item's triangle offset, and if the item reaches into the
-// block, its record and label, and marks the item's triangles of the
-// block with i in LDS. Thread r then finds its triangle's item j there:
-// t_in = t - itoff[j] is the triangle's index within the item, and the
-// record is item j's with t_in in bits 8-10. The per-triangle label array
-// (k_weld_verts_faces, k_vbase and the simplifier read it) is written here.
-__global__ __launch_bounds__(WELD_FIRST_BLK) void k_weld_first(
+struct WeldGeom {
+  uint32_t usx, usxy;  // voxel strides of y and z
+  float rx, ry, rz, shift;
+};
+
+// the vertex of a slot: doubled coordinates decoded from
+// slot = (lin * 3 + axis) * 2 | side
+__device__ __forceinline__ void write_slot_vertex(float *__restrict__ verts,
+                                                  uint64_t vid, uint32_t slot,
+                                                  const WeldGeom &g) {
+  const uint32_t eslot = slot >> 1;
+  const uint32_t axis = eslot % 3u;
+  const uint32_t lin = eslot / 3u;
+  const uint32_t vz = lin / g.usxy;
+  const uint32_t rem = lin - vz * g.usxy;
+  const uint32_t vy = rem / g.usx;
+  const uint32_t vx = rem - vy * g.usx;
+  const float dx = (float)(2 * vx + (axis == 0));
+  const float dy = (float)(2 * vy + (axis == 1));
+  const float dz = (float)(2 * vz + (axis == 2));
+  verts[3 * vid + 0] = (0.5f * dx + g.shift) * g.rx;
+  verts[3 * vid + 1] = (0.5f * dy + g.shift) * g.ry;
+  verts[3 * vid + 2] = (0.5f * dz + g.shift) * g.rz;
+}
+
+// LDS staging of one tile of WELD_BLK consecutive triangles of the stream,
+// which arrives per ITEM (k_emit): the triangles lie in at most WELD_BLK
+// consecutive items, since every item has at least one triangle. Thread i
+// takes item first + i: it loads the item's scan entry and record
+// (load_weld_item; neither address depends on the other, so a kernel can
+// have the next tile's pair in flight while it works on this one), stages
+// them, and marks the item's triangles of the tile with i. Thread r then
+// finds its triangle's item j = item[r]: t - off[j] is the triangle's index
+// within the item.
+struct WeldTile {
+  uint32_t off[WELD_BLK + 1];  // first triangle of items first .. first + 256
+  uint32_t voff[WELD_BLK];     // first global vertex id of the item
+  uint2 rec[WELD_BLK];
+  uint8_t item[WELD_BLK];
+  uint32_t next;  // items that end inside the tile (k_weld_label)
+};
+
+struct WeldItem {
+  uint64_t sc, sc_end;  // itscan of item first + i; of first + 256 (thread 0)
+  uint2 rec;
+};
+
+// items at or past i_end count as empty
+__device__ __forceinline__ WeldItem load_weld_item(
+    const uint2 *__restrict__ item_recs, const uint32_t *__restrict__ order,
+    const uint64_t *__restrict__ itscan, uint64_t first, uint64_t i_end) {
+  const uint64_t it = first + threadIdx.x;
+  WeldItem w;
+  w.sc = itscan[std::min<uint64_t>(it, i_end)];
+  w.sc_end = 0;
+  if (threadIdx.x == 0)
+    w.sc_end = itscan[std::min<uint64_t>(first + WELD_BLK, i_end)];
+  w.rec = make_uint2(0, 0);
+  if (it < i_end) w.rec = order ? item_recs[order[it]] : item_recs[it];
+  return w;
+}
+
+// Fill `w` for triangles [t0, t1), t1 <= t0 + WELD_BLK, from the loaded
+// items. Two barriers inside; the caller's next barrier must come before
+// the tile is staged again. With NEXT, w.next = how many of the items end at
+// or before t1: the item behind them holds triangle t1. It has one writer:
+// off[] ascends, so one i has off[i] <= t1 < off[i + 1], or none has and
+// thread 255 writes 256. Empty items past the range's end hold the
+// range's end in both entries, which is above t1 whenever a next tile exists.
+template <bool NEXT>
+__device__ __forceinline__ void stage_weld_tile(WeldTile &w,
+                                                const WeldItem &li,
+                                                uint32_t t0, uint32_t t1) {
+  w.off[threadIdx.x] = (uint32_t)li.sc;
+  w.voff[threadIdx.x] = (uint32_t)(li.sc >> 32);
+  w.rec[threadIdx.x] = li.rec;
+  if (threadIdx.x == 0) w.off[WELD_BLK] = (uint32_t)li.sc_end;
+  __syncthreads();
+  const uint32_t a = w.off[threadIdx.x], b = w.off[threadIdx.x + 1];
+  const uint32_t lo = std::max(a, t0), hi = std::min(b, t1);
+  for (uint32_t q = lo; q < hi; ++q) w.item[q - t0] = (uint8_t)threadIdx.x;
+  if (NEXT && a <= t1) {
+    if (b > t1) w.next = threadIdx.x;
+    else if (threadIdx.x == WELD_BLK - 1) w.next = WELD_BLK;
+  }
+  __syncthreads();
+}
+
+// the decoded corners of one triangle
+struct TriCorners {
+  uint32_t slot[3];
+  uint32_t first;  // bit v: corner v is its slot's first occurrence
+  uint32_t id[3];  // first corners: global vertex id
+};
+
+__device__ __forceinline__ TriCorners decode_tri(
+    const WeldTile &w, const uint16_t *s_pack, const uint16_t *s_ifirst,
+    const uint32_t *s_comb, uint32_t j, uint32_t t) {
+  const uint2 rec = w.rec[j];
+  const uint32_t tin = t - w.off[j];  // t within the item
+  const uint32_t mask = rec.y & 255u;
+  const uint32_t pk = s_pack[mask * MC_MAX_TRIS + tin];
+  const uint32_t ib = s_ifirst[mask * 8u + (~(rec.y >> 11) & 7u)];
+  const uint32_t cl3 = rec.x * 3u;
+  TriCorners c;
+  c.first = (ib >> (3u * tin)) & 7u;
+  #pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    const uint32_t nib = (pk >> (5 * v)) & 31u;
+    c.slot[v] = ((cl3 + s_comb[nib & 15u]) << 1) | (nib >> 4);
+    // rank = the item's first corners below bit 3 * tin + v
+    c.id[v] = w.voff[j] + (uint32_t)__popc(ib & ((1u << (3u * tin + v)) - 1u));
+  }
+  return c;
+}
+
+__device__ __forceinline__ void stage_item_first(uint16_t *s_ifirst) {
+  for (int k = threadIdx.x; k < 256 * 8; k += blockDim.x)
+    s_ifirst[k] = MC_ITEM_FIRST[k >> 3][k & 7];
+}
+
+// Vertex caps of the LDS weld's three bands, each twice the one below; the
+// table holds twice the cap (load <= 0.5). Larger labels take the global
+// table.
+#define WELD_LDS_CAP 8192u
+#define WELD_EMPTY 0xffffffffu  // no slot: slots are below 6 * nvox < 2^32
+
+// [5a] one workgroup per label whose vertex count nv is in (lo_cap, CAP]
+// (any other block exits): the whole weld of that label. The 8192 band's
+// 107 KB of LDS is one block per CU (gfx950: 160 KB per CU, all of it open
+// to one workgroup). The block walks
+// the label's triangles in stream order, one tile of WELD_BLK triangles at a
+// time, one thread per triangle (coalesced face stores). Per tile:
+//   1. stage the tile's items and decode the three slots of each triangle
+//   2. a first corner has local id = its global id - vbase[label]; it
+//      claims an entry of the open-addressing table with an LDS atomicCAS
+//      on the key (each slot has exactly one inserter), stores the id beside
+//      it, and writes its vertex
+//   3. barrier
+//   4. every other corner looks its slot up: its first occurrence sits
+//      earlier in the stream, so in this tile or an earlier one
+// The next tile's first item is the item that holds the triangle behind
+// this tile, found while the tile is staged; its loads are issued before
+// this tile's table work, which hides their latency.
+// Probe loops are bounded by the table size; a bound reached (a bug: the
+// band keeps the load at or below 0.5) raises *err and the call fails.
+template <uint32_t CAP>
+__global__ __launch_bounds__(WELD_BLK) void k_weld_label(
     const uint2 *__restrict__ item_recs,  // 8-B records, one per item
     const uint32_t *__restrict__ order,   // label partition permutation,
                                           // or null: records already sorted
-    const uint32_t *__restrict__ item_lab,  // sorted label id per item
-    const uint32_t *__restrict__ itoff,     // nitems + 1 triangle offsets
-    const uint32_t *__restrict__ blk_item,
-    uint32_t *__restrict__ lab_sorted,    // label id per triangle
-    uint32_t *__restrict__ slots_sorted,  // decoded 3 slots/tri (12 B)
-    uint32_t *__restrict__ wminp,
-    unsigned long long *__restrict__ bits,
-    int64_t sx, int64_t sxy,
-    uint64_t nitems, uint64_t ntris, uint64_t nwords) {
+    const uint64_t *__restrict__ itscan,  // nitems + 1 scan entries
+    const uint32_t *__restrict__ lab_item,
+    const uint32_t *__restrict__ tri_off,
+    const uint32_t *__restrict__ vbase,
+    uint32_t *__restrict__ lab_sorted,  // label id per triangle, or null
+    float *__restrict__ verts, uint32_t *__restrict__ faces,
+    WeldGeom g, uint32_t lo_cap, uint32_t *__restrict__ err) {
+  constexpr uint32_t TAB = 2 * CAP;
+  static_assert((TAB & (TAB - 1)) == 0 && CAP <= 65536, "");
+  constexpr uint32_t SHIFT = 32 - __builtin_ctz(TAB);
+  __shared__ uint32_t s_key[TAB];
+  __shared__ uint16_t s_val[TAB];
   __shared__ uint16_t s_pack[256 * MC_MAX_TRIS];
-  __shared__ uint8_t s_first[256 * MC_MAX_TRIS];
+  __shared__ uint16_t s_ifirst[256 * 8];
   __shared__ uint32_t s_comb[12];
-  __shared__ uint32_t s_need[12];
-  __shared__ uint32_t s_off[WELD_FIRST_BLK + 1];
-  __shared__ uint2 s_rec[WELD_FIRST_BLK];
-  __shared__ uint32_t s_lab[WELD_FIRST_BLK];
-  __shared__ uint8_t s_item[WELD_FIRST_BLK];
-  stage_decode_tables(s_pack, s_comb, sx, sxy);
-  for (int k = threadIdx.x; k < 256 * MC_MAX_TRIS; k += blockDim.x)
-    s_first[k] = MC_TRI_FIRST[k / MC_MAX_TRIS][k % MC_MAX_TRIS];
-  if (threadIdx.x < 12) s_need[threadIdx.x] = MC_EDGE_NEED[threadIdx.x];
-  const uint64_t t = (uint64_t)blockIdx.x * WELD_FIRST_BLK + threadIdx.x;
-  const uint32_t t0 = blockIdx.x * WELD_FIRST_BLK;  // < ntris < 2^32
-  // offsets of items first .. first + 256, clamped to itoff[nitems] = ntris
-  const uint64_t first = blk_item[blockIdx.x];
-  const uint64_t it = first + threadIdx.x;
-  s_off[threadIdx.x] = itoff[std::min<uint64_t>(it, nitems)];
-  if (threadIdx.x == 0)
-    s_off[WELD_FIRST_BLK] =
-        itoff[std::min<uint64_t>(first + WELD_FIRST_BLK, nitems)];
-  __syncthreads();
-  {
-    // the item's triangles inside the block (none for items past its end
-    // or past nitems: their range is empty)
-    const uint32_t lo = std::max(s_off[threadIdx.x], t0);
-    const uint32_t hi = std::min<uint32_t>(s_off[threadIdx.x + 1],
-                                           t0 + WELD_FIRST_BLK);
-    if (lo < hi) {
-      s_rec[threadIdx.x] = order ? item_recs[order[it]] : item_recs[it];
-      s_lab[threadIdx.x] = item_lab[it];
-      for (uint32_t q = lo; q < hi; ++q)
-        s_item[q - t0] = (uint8_t)threadIdx.x;
+  __shared__ WeldTile s_tile;
+  const uint32_t l = blockIdx.x;
+  const uint32_t vb = vbase[l];
+  const uint32_t nv = vbase[l + 1] - vb;
+  if (nv <= lo_cap || nv > CAP) return;
+  const uint32_t t_end = tri_off[l + 1];
+  const uint64_t i_end = lab_item[l + 1];
+  uint64_t first = lab_item[l];
+  WeldItem li = load_weld_item(item_recs, order, itscan, first, i_end);
+  stage_decode_tables(s_pack, s_comb, g.usx, g.usxy);
+  stage_item_first(s_ifirst);
+  for (uint32_t k = threadIdx.x; k < TAB; k += WELD_BLK) s_key[k] = WELD_EMPTY;
+  for (uint32_t t0 = tri_off[l]; t0 < t_end; t0 += WELD_BLK) {
+    const uint32_t t1 = std::min(t0 + WELD_BLK, t_end);
+    stage_weld_tile<true>(s_tile, li, t0, t1);
+    // the next tile's items, in flight while this tile is welded (s_tile.next
+    // is not written again before the barrier below)
+    if (t1 < t_end) {
+      first += s_tile.next;
+      li = load_weld_item(item_recs, order, itscan, first, i_end);
+    }
+    const uint32_t t = t0 + threadIdx.x;
+    TriCorners c;
+    if (t < t1) {
+      c = decode_tri(s_tile, s_pack, s_ifirst, s_comb,
+                     s_tile.item[threadIdx.x], t);
+      #pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        if (!((c.first >> v) & 1u)) continue;
+        uint32_t pos = (c.slot[v] * 2654435761u) >> SHIFT;
+        uint32_t n = 0;
+        for (; n < TAB; ++n) {
+          if (atomicCAS(&s_key[pos], WELD_EMPTY, c.slot[v]) == WELD_EMPTY)
+            break;
+          pos = (pos + 1) & (TAB - 1);
+        }
+        if (n == TAB) atomicOr(err, 1u);
+        else s_val[pos] = (uint16_t)(c.id[v] - vb);
+        write_slot_vertex(verts, c.id[v], c.slot[v], g);
+      }
+    }
+    __syncthreads();
+    if (t < t1) {
+      #pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        uint32_t id = c.id[v] - vb;
+        if (!((c.first >> v) & 1u)) {
+          uint32_t pos = (c.slot[v] * 2654435761u) >> SHIFT;
+          uint32_t n = 0, key;
+          while ((key = s_key[pos]) != c.slot[v] && key != WELD_EMPTY &&
+                 ++n < TAB)
+            pos = (pos + 1) & (TAB - 1);
+          id = s_val[pos];
+          if (key != c.slot[v]) atomicOr(err, 2u);  // absent
+        }
+        faces[3ull * t + v] = id;
+      }
+      if (lab_sorted) lab_sorted[t] = l;
     }
   }
-  __syncthreads();
+}
+
+// [5b] one wave per label: a label above WELD_LDS_CAP vertices appends the
+// WELD_BLK-triangle blocks of the stream that hold its triangles to
+// blk_list (in no particular order) and counts itself. Its first block is
+// left out when an earlier such label, which has listed it, reaches into
+// it. The cost follows those labels' triangles, not the stream's.
+__global__ void k_weld_plan(const uint32_t *__restrict__ tri_off,
+                            const uint32_t *__restrict__ vbase,
+                            uint32_t nlabels, uint32_t *__restrict__ blk_list,
+                            uint32_t *__restrict__ nlist,
+                            uint32_t *__restrict__ ntable) {
+  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
-  bool f[3] = {false, false, false};  // tail lanes contribute 0
-  if (t < ntris) {
-    const uint32_t j = s_item[threadIdx.x];
-    uint2 rec = s_rec[j];
-    rec.y |= ((uint32_t)t - s_off[j]) << 8;  // t within the item
-    lab_sorted[t] = s_lab[j];
-    const uint32_t ti = (rec.y & 255u) * MC_MAX_TRIS + ((rec.y >> 8) & 7u);
-    const uint32_t pk = s_pack[ti];
-    const uint32_t fb = s_first[ti];
-    const uint32_t interior = ~(rec.y >> 11) & 7u;  // axes with c_b > 0
-    const uint32_t cl3 = rec.x * 3u;
-    #pragma unroll
-    for (int v = 0; v < 3; ++v) {
-      const uint32_t nib = (pk >> (5 * v)) & 31u;
-      const uint32_t e = nib & 15u;
-      const uint32_t slot = ((cl3 + s_comb[e]) << 1) | (nib >> 4);
-      slots_sorted[3 * t + v] = slot;
-      f[v] = ((fb >> v) & 1u) && (s_need[e] & interior) == 0;
-      if (f[v]) wminp[slot] = (uint32_t)(3 * t + v);
+  const uint64_t l = gid / WAVE;
+  if (l >= nlabels) return;
+  if (vbase[l + 1] - vbase[l] <= WELD_LDS_CAP) return;
+  uint32_t b0 = tri_off[l] / WELD_BLK;
+  const uint32_t b1 = (tri_off[l + 1] - 1) / WELD_BLK;
+  // label m - 1 ends in block b0 or later while tri_off[m] > b0 * WELD_BLK;
+  // every label has a triangle, so this looks at fewer than WELD_BLK labels
+  for (uint64_t m = l; m > 0 && tri_off[m] > b0 * WELD_BLK; --m)
+    if (vbase[m] - vbase[m - 1] > WELD_LDS_CAP) {
+      ++b0;  // listed by label m - 1 (b0 <= b1 + 1 now: n may be 0)
+      break;
+    }
+  const uint32_t n = b1 + 1 - b0;
+  uint32_t base = 0;
+  if (lane == 0) {
+    base = atomicAdd(nlist, n);
+    atomicAdd(ntable, 1u);
+  }
+  base = __shfl(base, 0);
+  for (uint32_t k = lane; k < n; k += WAVE) blk_list[base + k] = b0 + k;
+}
+
+// [5c] the global table, first pass: block i takes the stream's block
+// blk_list[i], one thread per triangle. A triangle of a label that the LDS
+// weld has done is skipped (label WELD_EMPTY in its slot quad). For the
+// others: decode the three slots, write the quad (3 slots + label id), and
+// for each first corner store its global vertex id into wminp[slot] with a
+// plain store (one writer per slot) and write its vertex. The table is
+// never cleared: every slot k_weld_faces reads was stored here, in this
+// call, by the first corner of the same label.
+__global__ __launch_bounds__(WELD_BLK) void k_weld_first(
+    const uint2 *__restrict__ item_recs, const uint32_t *__restrict__ order,
+    const uint32_t *__restrict__ item_lab,  // sorted label id per item
+    const uint64_t *__restrict__ itscan,
+    const uint32_t *__restrict__ blk_item,
+    const uint32_t *__restrict__ blk_list,
+    const uint32_t *__restrict__ vbase,
+    uint4 *__restrict__ quads,  // per listed triangle
+    uint32_t *__restrict__ wminp,
+    uint32_t *__restrict__ lab_sorted,  // label id per triangle, or null
+    float *__restrict__ verts, WeldGeom g, uint64_t nitems, uint32_t ntris) {
+  __shared__ uint16_t s_pack[256 * MC_MAX_TRIS];
+  __shared__ uint16_t s_ifirst[256 * 8];
+  __shared__ uint32_t s_comb[12];
+  __shared__ WeldTile s_tile;
+  stage_decode_tables(s_pack, s_comb, g.usx, g.usxy);
+  stage_item_first(s_ifirst);
+  const uint32_t b = blk_list[blockIdx.x];
+  const uint32_t t0 = b * WELD_BLK;  // < ntris < 2^32
+  const uint32_t t1 = std::min(t0 + WELD_BLK, ntris);
+  const uint64_t first = blk_item[b];
+  stage_weld_tile<false>(
+      s_tile, load_weld_item(item_recs, order, itscan, first, nitems), t0,
+                  t1);
+  const uint32_t t = t0 + threadIdx.x;
+  uint4 quad = make_uint4(0, 0, 0, WELD_EMPTY);
+  if (t < t1) {
+    const uint32_t j = s_tile.item[threadIdx.x];
+    const uint32_t l = item_lab[first + j];
+    if (vbase[l + 1] - vbase[l] > WELD_LDS_CAP) {
+      const TriCorners c = decode_tri(s_tile, s_pack, s_ifirst, s_comb, j, t);
+      #pragma unroll
+      for (int v = 0; v < 3; ++v)
+        if ((c.first >> v) & 1u) {
+          wminp[c.slot[v]] = c.id[v];
+          write_slot_vertex(verts, c.id[v], c.slot[v], g);
+        }
+      quad = make_uint4(c.slot[0], c.slot[1], c.slot[2], l);
+      if (lab_sorted) lab_sorted[t] = l;
     }
   }
-  const unsigned long long bal[3] = {__ballot(f[0]), __ballot(f[1]),
-                                     __ballot(f[2])};
-  const uint64_t w0 = (t / WAVE) * 3;  // wave-uniform
-  #pragma unroll
-  for (uint32_t j = 0; j < 3; ++j) {
-    const uint32_t c = 64 * j + lane;  // corner within the wave's 192
-    const uint32_t q = c / 3, r = c - 3 * q;
-    const unsigned long long src = r == 0 ? bal[0] : (r == 1 ? bal[1] : bal[2]);
-    const unsigned long long word = __ballot((src >> q) & 1ull);
-    if (lane == j && w0 + j < nwords) bits[w0 + j] = word;
-  }
+  quads[(uint64_t)blockIdx.x * WELD_BLK + threadIdx.x] = quad;
 }
 
-struct PopcWord {
-  __device__ uint32_t operator()(unsigned long long w) const {
-    return (uint32_t)__popcll(w);
-  }
-};
-
-// vertex id of corner i (must be below its word's scan base + rank)
-__device__ __forceinline__ uint32_t vtx_id_of(
-    const uint32_t *__restrict__ wscan,
-    const unsigned long long *__restrict__ bits, uint64_t i) {
-  uint64_t w = i >> 6;
-  unsigned long long mask = (1ull << (i & 63)) - 1;
-  return wscan[w] + (uint32_t)__popcll(bits[w] & mask);
-}
-
-__global__ void k_total_verts(const uint32_t *__restrict__ wscan,
-                              const unsigned long long *__restrict__ bits,
-                              uint64_t nwords, uint32_t *out) {
-  *out = wscan[nwords - 1] + (uint32_t)__popcll(bits[nwords - 1]);
-}
-
-// [5d] per-label vertex bases: vbase[l] = vtx_scan at the label's first corner
-__global__ void k_vbase(const uint32_t *__restrict__ tri_off,
-                        const uint32_t *__restrict__ wscan,
-                        const unsigned long long *__restrict__ bits,
-                        uint32_t *__restrict__ vbase,
-                        uint32_t nlabels, uint64_t total_verts) {
-  uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l > nlabels) return;
-  if (l == nlabels) vbase[l] = (uint32_t)total_verts;
-  else vbase[l] = vtx_id_of(wscan, bits, 3ull * tri_off[l]);
-}
-
-// [5e] vertices + faces in one pass, one thread per triangle. A corner's
-// vertex id is a pure function of its first stream position p:
-// wscan[p>>6] + popc(bits[p>>6] below bit p&63). A flagged corner (first
-// occurrence, ~1/6 of corners) is its own first position: it takes the id
-// from its own word, decodes the coordinates from its slot and writes the
-// vertex. An unflagged corner gathers p = wminp[slot]; a label's corners
-// are contiguous in the stream, so both that gather and the bits/wscan
-// lookup (12 B per 64 corners) are cache-local.
-// No vertex-id table: faces need nothing the vertex writes produce.
-// Label id from the per-triangle label array that k_weld_first wrote.
-__global__ void k_weld_verts_faces(const uint32_t *__restrict__ slots,
-                                   const uint32_t *__restrict__ wminp,
-                                   const uint32_t *__restrict__ lab_sorted,
-                                   const uint32_t *__restrict__ wscan,
-                                   const unsigned long long *__restrict__ bits,
-                                   const uint32_t *__restrict__ vbase,
-                                   float *__restrict__ verts,
-                                   uint32_t *__restrict__ faces,
-                                   uint32_t usx, uint32_t usxy,
-                                   float rx, float ry, float rz, float shift,
-                                   uint64_t ntris) {
-  uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ntris) return;
-  const uint32_t e[3] = {slots[3 * t], slots[3 * t + 1], slots[3 * t + 2]};
-  const uint32_t base = vbase[lab_sorted[t]];
-  // corners 3t..3t+2 straddle two words when they start at bit 62 or 63
-  // (3 does not divide 64); the second word exists since 3t+2 < 3*ntris
-  const uint64_t w0 = (3 * t) >> 6;
-  const uint32_t b0 = (uint32_t)((3 * t) & 63);
-  const bool straddle = b0 > 61;
-  const unsigned long long word0 = bits[w0];
-  const uint32_t scan0 = wscan[w0];
-  const unsigned long long word1 = straddle ? bits[w0 + 1] : 0ull;
-  const uint32_t scan1 = straddle ? wscan[w0 + 1] : 0u;
-  #pragma unroll
-  for (int v = 0; v < 3; ++v) {
-    uint32_t b = b0 + v;
-    const bool second = b > 63;
-    const unsigned long long word = second ? word1 : word0;
-    b &= 63;
-    uint32_t vid;
-    if ((word >> b) & 1ull) {
-      vid = (second ? scan1 : scan0) +
-            (uint32_t)__popcll(word & ((1ull << b) - 1));
-      // doubled coordinates decoded from the slot (first occurrences
-      // only): slot = (lin*3 + axis)*2 | side
-      uint32_t eslot = e[v] >> 1;
-      uint32_t axis = eslot % 3u;
-      uint32_t lin = eslot / 3u;
-      uint32_t vz = lin / usxy;
-      uint32_t rem = lin - vz * usxy;
-      uint32_t vy = rem / usx;
-      uint32_t vx = rem - vy * usx;
-      float dx = (float)(2 * vx + (axis == 0));
-      float dy = (float)(2 * vy + (axis == 1));
-      float dz = (float)(2 * vz + (axis == 2));
-      verts[3ull * vid + 0] = (0.5f * dx + shift) * rx;
-      verts[3ull * vid + 1] = (0.5f * dy + shift) * ry;
-      verts[3ull * vid + 2] = (0.5f * dz + shift) * rz;
-    } else {
-      vid = vtx_id_of(wscan, bits, wminp[e[v]]);
-    }
-    faces[3 * t + v] = vid - base;
-  }
+// [5d] the global table, second pass over the same list: a corner's face
+// index is the id its slot's first corner stored, made local to the label
+__global__ void k_weld_faces(const uint4 *__restrict__ quads,
+                             const uint32_t *__restrict__ blk_list,
+                             const uint32_t *__restrict__ wminp,
+                             const uint32_t *__restrict__ vbase,
+                             uint32_t *__restrict__ faces) {
+  const uint4 q = quads[(uint64_t)blockIdx.x * WELD_BLK + threadIdx.x];
+  if (q.w == WELD_EMPTY) return;
+  const uint64_t t = (uint64_t)blk_list[blockIdx.x] * WELD_BLK + threadIdx.x;
+  const uint32_t base = vbase[q.w];
+  faces[3 * t + 0] = wminp[q.x] - base;
+  faces[3 * t + 1] = wminp[q.y] - base;
+  faces[3 * t + 2] = wminp[q.z] - base;
 }
 
 __global__ void k_iota(uint32_t *p, uint64_t n) {
@@ -921,6 +1082,7 @@ mg_ctx *mg_init(int device_id) {
   if (hipSetDevice(device_id) != hipSuccess) return nullptr;
   mg_ctx *c = new mg_ctx();
   c->device = device_id;
+  c->stats.weld_lds_cap = WELD_LDS_CAP;
   bool ok =
       hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) ==
           hipSuccess &&
@@ -996,12 +1158,13 @@ struct ChunkCall {
   uint64_t V;              // vertices (run_weld; run_simplify)
   // run_partition: label id per item (the sort's key output), the 8-B
   // item records the weld reads and the permutation to read them through
-  // (null when the records themselves were sorted), the slot triples
+  // (null when the records themselves were sorted)
   const uint32_t *item_lab;
   const uint2 *rec_src;
   const uint32_t *order_sorted;
-  uint32_t *slots;
-  uint32_t *lab_sorted;    // label id per triangle (run_weld writes it)
+  bool simplify;           // a simplify follows the weld
+  uint32_t *lab_sorted;    // label id per triangle (run_weld writes it when
+                           // a simplify follows, else null)
 };
 
 static void set_hole_stash(mg_ctx *c, const ChunkCall &k) {
@@ -1205,40 +1368,27 @@ static int run_count_emit(mg_ctx *c, ChunkCall &k) {
   return 0;
 }
 
-struct TriSortView {
-  uint64_t *recs, *recs_alt;  // the 8-B item records as the sort's u64 values
-  uint32_t *slots;            // decoded slot triples, per triangle
-};
-
-// c->keys_sorted (2 NI + 3 T u32 for NI items of T triangles): [sort
-// alternate of tri_keys, 2 NI words][slot triples, 3 T words]
-static TriSortView tri_sort_view(mg_ctx *c, uint64_t NI) {
-  return {reinterpret_cast<uint64_t *>(c->tri_keys.get()),
-          reinterpret_cast<uint64_t *>(c->keys_sorted.get()),
-          c->keys_sorted.get() + 2 * NI};
-}
-
-// [4] stable partition of the ITEMS by label id, then the items' triangle
-// offsets. Default (MG_SORT_RECS=0 reverts): the 8-B records ride the
-// radix sort as its 64-bit VALUES, so the weld reads them back
-// SEQUENTIALLY instead of paying a random 8-B gather through the
-// permutation.
+// [4] stable partition of the ITEMS by label id, then the item scan.
+// Default (MG_SORT_RECS=0 reverts): the 8-B records ride the radix sort as
+// its 64-bit VALUES, so the weld reads them back SEQUENTIALLY instead of
+// paying a random 8-B gather through the permutation.
 static int run_partition(mg_ctx *c, ChunkCall &k) {
   hipStream_t s = c->stream;
   const uint64_t T = k.T, NI = k.NI;
   const char *sre = getenv("MG_SORT_RECS");
   const bool sort_recs = !(sre && sre[0] == '0');
-  if (ensure(c, c->keys_sorted, 2 * NI + 3 * T)) return 19;
   if (ensure(c, c->tri_label_alt, NI)) return 19;
-  const TriSortView tv = tri_sort_view(c, NI);
-  k.slots = tv.slots;
   const dim3 nb((uint32_t)((NI + 255) / 256)), blk(256);
   unsigned end_bit = 1;
   while ((1u << end_bit) < k.nlabels) ++end_bit;
   rocprim::double_buffer<uint32_t> d_keys(c->tri_label.get(),
                                           c->tri_label_alt.get());
   if (sort_recs) {
-    rocprim::double_buffer<uint64_t> d_vals(tv.recs, tv.recs_alt);
+    // the 8-B item records as the sort's u64 values
+    if (ensure(c, c->keys_sorted, 2 * NI)) return 19;
+    rocprim::double_buffer<uint64_t> d_vals(
+        reinterpret_cast<uint64_t *>(c->tri_keys.get()),
+        reinterpret_cast<uint64_t *>(c->keys_sorted.get()));
     if (int e = sort_pairs(c, d_keys, d_vals, NI, 0u, end_bit, s,
                            "radix_sort size query failed",
                            "radix_sort failed", 19))
@@ -1259,100 +1409,127 @@ static int run_partition(mg_ctx *c, ChunkCall &k) {
     k.order_sorted = d_vals.current();
   }
   k.item_lab = d_keys.current();
-  // itoff[1..NI] = inclusive scan of the sorted items' triangle counts
-  // (itoff[NI] = T); k_label_ranges stores itoff[0]
-  if (ensure(c, c->itoff, NI + 1)) return 19;
-  uint32_t *itoff = c->itoff.get();
+  // itscan[1..NI] = inclusive scan of the sorted items' (vertices <<
+  // 32) | triangles; k_label_ranges stores itscan[0]
+  if (ensure(c, c->itscan, NI + 1)) return 19;
+  uint64_t *itscan = c->itscan.get();
   if (int e = k.order_sorted
-          ? scan_incl_u32(c, rocprim::make_transform_iterator(
-                                 k.order_sorted, ItemTrisVia{k.rec_src}),
-                          itoff + 1, NI, s, "item scan size query failed",
+          ? scan_incl_u64(c, rocprim::make_transform_iterator(
+                                 k.order_sorted, ItemCountsVia{k.rec_src}),
+                          itscan + 1, NI, s, "item scan size query failed",
                           "item scan failed", 19)
-          : scan_incl_u32(c, rocprim::make_transform_iterator(
-                                 k.rec_src, ItemTris{}),
-                          itoff + 1, NI, s, "item scan size query failed",
+          : scan_incl_u64(c, rocprim::make_transform_iterator(
+                                 k.rec_src, ItemCounts{}),
+                          itscan + 1, NI, s, "item scan size query failed",
                           "item scan failed", 19))
     return e;
-  // label ranges + the weld blocks' first items
-  if (ensure(c, c->tri_off, (uint64_t)k.nlabels + 1)) return 19;
-  if (ensure(c, c->blk_item, (T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK))
-    return 19;
-  hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.item_lab, itoff,
-                     c->tri_off.get(), c->blk_item.get(), NI, T, k.nlabels);
+  // per-label ranges + the first items of the stream's blocks
+  const uint64_t nl1 = (uint64_t)k.nlabels + 1;
+  if (ensure(c, c->tri_off, nl1)) return 19;
+  if (ensure(c, c->lab_item, nl1)) return 19;
+  if (ensure(c, c->vbase, nl1)) return 19;
+  if (ensure(c, c->blk_item, (T + WELD_BLK - 1) / WELD_BLK)) return 19;
+  hipLaunchKernelGGL(k_label_ranges, nb, blk, 0, s, k.item_lab, itscan,
+                     c->tri_off.get(), c->lab_item.get(), c->vbase.get(),
+                     c->blk_item.get(), NI, k.nlabels);
   HIP_TRY(c, hipGetLastError(), 19);
   HIP_TRY(c, hipEventRecord(c->ev[EV_PARTITION_END], s), 19);
   return 0;
 }
 
-struct WeldScanView {
-  unsigned long long *bits;  // first-occurrence flags, one bit per corner
-  uint32_t *wscan;           // exclusive scan of the words' popcounts
-};
-
-// c->vtx_scan (NC u32 for NC corners) for the weld: [bits, nwords u64]
-// [wscan, nwords u32], nwords = ceil(NC / 64), so 3 * nwords <= NC words.
-// The simplifier, which runs after the weld is done with it, takes the
-// whole buffer as its u32 vertex renumbering (simp_finalize).
-static WeldScanView weld_scan_view(mg_ctx *c, uint64_t nwords) {
-  return {reinterpret_cast<unsigned long long *>(c->vtx_scan.get()),
-          c->vtx_scan.get() + 2 * nwords};
+static int check_weld_err(mg_ctx *c) {
+  const uint32_t werr = *c->h_weld_err.get();
+  if (!werr) return 0;
+  SET_ERR(c, "weld: a label table probe reached its bound (flag %u)", werr);
+  return 29;
 }
 
-// [5] weld — direct-addressed (edge, side) table, collision-free
+// [5] weld: per-label LDS tables in three vertex-count bands, and the global
+// direct-addressed table for the labels above WELD_LDS_CAP (see "welding")
 static int run_weld(mg_ctx *c, ChunkCall &k) {
   hipStream_t s = c->stream;
   const uint64_t T = k.T, NC = 3 * T;  // corners
   const uint64_t wslots = 6 * k.nvox;  // 3 edges/voxel x 2 sides
   if (wslots >= (1ull << 32)) {
-    SET_ERR(c, "chunk too large for the 32-bit weld table (%d x %d x %d); "
+    SET_ERR(c, "chunk too large for the 32-bit weld slots (%d x %d x %d); "
             "split the task shape (the reference's own mesher bound is "
             "1023x1023x511, igneous_cli/cli.py:1049-1052)", k.sx, k.sy, k.sz);
     return 20;
   }
-  if (ensure(c, c->wh_keys, wslots)) return 20;   // wminp
-  if (ensure(c, c->vtx_scan, NC)) return 20;
-  if (ensure(c, c->lab_sorted, T)) return 20;
-  k.lab_sorted = c->lab_sorted.get();
-  // not cleared: k_weld_first stores every slot that is read afterwards
-  uint32_t *wminp = c->wh_keys.get();
-  const dim3 nbt((uint32_t)((T + 255) / 256)), blk(256);
-  // first positions + first-occurrence flags as a bit array, then a
-  // word-granular scan
-  const uint64_t nwords = (NC + 63) / 64;
-  auto [bits, wscan] = weld_scan_view(c, nwords);
-  hipLaunchKernelGGL(k_weld_first,
-                     dim3((uint32_t)((T + WELD_FIRST_BLK - 1) / WELD_FIRST_BLK)),
-                     dim3(WELD_FIRST_BLK), 0, s, k.rec_src, k.order_sorted,
-                     k.item_lab, c->itoff.get(), c->blk_item.get(),
-                     k.lab_sorted, k.slots, wminp, bits, k.g.sx,
-                     k.g.sx * k.g.sy, k.NI, T, nwords);
-  if (int e = scan_u32(c, rocprim::make_transform_iterator(bits, PopcWord{}),
-                       wscan, nwords, s, "weld scan size query failed",
-                       "weld scan failed", 20))
-    return e;
-  uint32_t *d_tv = &c->scalars->weld_verts;
-  hipLaunchKernelGGL(k_total_verts, dim3(1), dim3(1), 0, s, wscan, bits,
-                     nwords, d_tv);
-  uint32_t tv = 0;
-  HIP_TRY(c, hipMemcpyAsync(&tv, d_tv, 4, hipMemcpyDeviceToHost, s), 21);
+  const uint32_t nblocks = (uint32_t)((T + WELD_BLK - 1) / WELD_BLK);
+  if (ensure(c, c->blk_list, nblocks)) return 20;
+  if (ensure(c, c->h_weld_err, 1)) return 20;
+  *c->h_weld_err.get() = 0;
+  hipLaunchKernelGGL(k_weld_plan,
+                     dim3((uint32_t)(((uint64_t)k.nlabels * WAVE + 255) / 256)),
+                     dim3(256), 0, s, c->tri_off.get(), c->vbase.get(),
+                     k.nlabels, c->blk_list.get(), &c->scalars->weld_nlist,
+                     &c->scalars->weld_table_labels);
+  // the one host sync: vertex total (the scan's last element) and the plan
+  uint64_t tot = 0;
+  uint32_t plan[2] = {0, 0};  // weld_nlist, weld_table_labels
+  HIP_TRY(c, hipMemcpyAsync(&tot, c->itscan.get() + k.NI, 8,
+                            hipMemcpyDeviceToHost, s), 21);
+  HIP_TRY(c, hipMemcpyAsync(plan, &c->scalars->weld_nlist, 8,
+                            hipMemcpyDeviceToHost, s), 21);
   HIP_TRY(c, hipStreamSynchronize(s), 21);
-  k.V = tv;
-  c->stats.total_verts = tv;
+  k.V = tot >> 32;
+  const uint64_t nlist = plan[0];
+  c->stats.total_verts = k.V;
+  c->stats.weld_table_labels = plan[1];
+  c->stats.weld_lds_labels = k.nlabels - plan[1];
 
   if (ensure(c, c->verts, 3 * k.V)) return 22;
   if (ensure(c, c->faces, NC)) return 22;
-  if (ensure(c, c->vbase, (uint64_t)k.nlabels + 1)) return 22;
-  // vbase depends only on the scan, so it goes first
-  hipLaunchKernelGGL(k_vbase, dim3((k.nlabels + 1 + 255) / 256), dim3(256),
-                     0, s, c->tri_off.get(), wscan, bits, c->vbase.get(),
-                     k.nlabels, k.V);
-  hipLaunchKernelGGL(k_weld_verts_faces, nbt, blk, 0, s, k.slots, wminp,
-                     k.lab_sorted, wscan, bits, c->vbase.get(),
-                     c->verts.get(), c->faces.get(), (uint32_t)k.g.sx,
-                     (uint32_t)(k.g.sx * k.g.sy), k.rx, k.ry, k.rz,
-                     k.voxel_centered ? 0.0f : 0.5f, T);
+  k.lab_sorted = nullptr;
+  if (k.simplify) {
+    if (ensure(c, c->lab_sorted, T)) return 22;
+    // simp_finalize's scratch: newid[vbase[l]] is read for every l <= nlabels
+    if (ensure(c, c->vtx_scan, k.V + 1)) return 22;
+    k.lab_sorted = c->lab_sorted.get();
+  }
+  const WeldGeom wg = {(uint32_t)k.g.sx, (uint32_t)(k.g.sx * k.g.sy),
+                       k.rx, k.ry, k.rz, k.voxel_centered ? 0.0f : 0.5f};
+  uint32_t *d_err = &c->scalars->weld_err;
+  if (plan[1] < k.nlabels) {
+    // bands (lo_cap, CAP] of 1, 2 and 4 blocks per CU, the fewest first
+    auto launch_band = [&](auto capc, uint32_t lo_cap) {
+      hipLaunchKernelGGL(k_weld_label<decltype(capc)::value>, dim3(k.nlabels),
+                         dim3(WELD_BLK), 0, s, k.rec_src, k.order_sorted,
+                         c->itscan.get(), c->lab_item.get(), c->tri_off.get(),
+                         c->vbase.get(), k.lab_sorted, c->verts.get(),
+                         c->faces.get(), wg, lo_cap, d_err);
+    };
+    launch_band(std::integral_constant<uint32_t, WELD_LDS_CAP>{},
+                WELD_LDS_CAP / 2);
+    launch_band(std::integral_constant<uint32_t, WELD_LDS_CAP / 2>{},
+                WELD_LDS_CAP / 4);
+    launch_band(std::integral_constant<uint32_t, WELD_LDS_CAP / 4>{}, 0u);
+  }
+  if (nlist > 0) {
+    // only now: the table is 24 B per voxel
+    if (ensure(c, c->wh_keys, wslots)) return 22;
+    if (ensure(c, c->weld_quads, nlist * WELD_BLK)) return 22;
+    hipLaunchKernelGGL(k_weld_first, dim3((uint32_t)nlist), dim3(WELD_BLK), 0,
+                       s, k.rec_src, k.order_sorted, k.item_lab,
+                       c->itscan.get(), c->blk_item.get(), c->blk_list.get(),
+                       c->vbase.get(), c->weld_quads.get(), c->wh_keys.get(),
+                       k.lab_sorted, c->verts.get(), wg, k.NI, (uint32_t)T);
+    hipLaunchKernelGGL(k_weld_faces, dim3((uint32_t)nlist), dim3(WELD_BLK), 0,
+                       s, c->weld_quads.get(), c->blk_list.get(),
+                       c->wh_keys.get(), c->vbase.get(), c->faces.get());
+  }
   HIP_TRY(c, hipGetLastError(), 22);
+  HIP_TRY(c, hipMemcpyAsync(c->h_weld_err.get(), d_err, 4,
+                            hipMemcpyDeviceToHost, s), 22);
   HIP_TRY(c, hipEventRecord(c->ev[EV_WELD_END], s), 22);
+  // The simplifier indexes vertices by the face ids, so the probe-bound flag
+  // is checked before it runs; every other call copies the faces without
+  // following them and checks behind its last sync (mesh_chunk_impl).
+  if (k.simplify) {
+    HIP_TRY(c, hipStreamSynchronize(s), 22);
+    if (int e = check_weld_err(c)) return e;
+  }
   return 0;
 }
 
@@ -1473,6 +1650,7 @@ static int mesh_chunk_impl(mg_ctx *c, const ChunkRequest &r) {
   g.nseg = g.nsegx * g.ncy * g.ncz;
 
   memset(&c->stats, 0, sizeof(c->stats));
+  c->stats.weld_lds_cap = WELD_LDS_CAP;
   c->stats.bytes_read_algorithmic = k.nvox * k.esize;
   hipStream_t s = c->stream;
 
@@ -1509,10 +1687,11 @@ static int mesh_chunk_impl(mg_ctx *c, const ChunkRequest &r) {
     write_stage_times(c, r, false);
     return 0;
   }
+  k.simplify = r.reduction_factor > 1;
   if (int e = run_partition(c, k)) return e;
   if (int e = run_weld(c, k)) return e;
   // [6] per-label quadric simplification (mesh.py:376-381 semantics)
-  if (r.reduction_factor > 1 && k.T > 0)
+  if (k.simplify)
     if (int e = run_simplify(c, k.nlabels, k.lab_sorted, r.reduction_factor,
                              r.max_error, &k.T, &k.V))
       return e;
@@ -1522,6 +1701,11 @@ static int mesh_chunk_impl(mg_ctx *c, const ChunkRequest &r) {
     return e;
   HIP_TRY(c, hipEventRecord(c->ev[EV_END], s), 25);
   HIP_TRY(c, hipStreamSynchronize(s), 25);
+  if (int e = check_weld_err(c)) {
+    if (r.bout) { mg_blobset_free(*r.bout); *r.bout = nullptr; }
+    else { mg_meshset_free(*r.out); *r.out = nullptr; }
+    return e;
+  }
   write_stage_times(c, r, true);
   return 0;
 }
@@ -1786,7 +1970,7 @@ int mg_simplify_mesh(mg_ctx *c,
     if (ensure(c, c->tri_off, 2)) return 10;
     if (ensure(c, c->vbase, 2)) return 10;
     if (ensure(c, c->tri_label, T + 1)) return 10;
-    // simp_finalize's vertex renumbering (weld_scan_view)
+    // simp_finalize's vertex renumbering
     if (ensure(c, c->vtx_scan, std::max<uint64_t>(V + 1, 3 * T))) return 10;
     HIP_TRY(c, hipMemcpyAsync(c->verts.get(), verts, V * 12,
                               hipMemcpyHostToDevice, s), 11);

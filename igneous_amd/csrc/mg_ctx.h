@@ -69,14 +69,16 @@ struct LabelVolume : DevBuf {
 // arithmetic on the device pointer, never dereferenced on the host). No
 // field carries a value between calls — each is memset or stored on the
 // device inside the call that reads it: the hash words by label_hash_reset
-// (which clears the whole block), map_err by run_label_map, weld_verts by
-// k_total_verts, the simp_* totals by k_last_sum, simp_prof by run_simplify,
+// (which clears the whole block, so the weld_* words start every chunk call
+// at 0), map_err by run_label_map, the simp_* totals by k_last_sum, simp_prof by run_simplify,
 // cv_cursor by run_count_voxels' own label_hash_reset.
 struct CtxScalars {
   uint32_t lh_counter;       // label hash: next dense id = labels so far
   uint32_t lh_overflow;      // label hash: a probe sequence ran out
   uint32_t map_err;          // run_label_map: MAP_ERR_* bits
-  uint32_t weld_verts;       // run_weld: vertex total
+  uint32_t weld_nlist;       // k_weld_plan: listed blocks of the table path
+  uint32_t weld_table_labels;  // k_weld_plan: labels above WELD_LDS_CAP
+  uint32_t weld_err;         // k_weld_label: a probe loop hit its bound
   uint32_t simp_kept;        // park_inactive / simp_global_round: faces kept
   uint32_t simp_new_verts;   // simp_finalize: referenced vertices
   uint32_t simp_final_tris;  // simp_finalize: final triangle total
@@ -86,6 +88,9 @@ struct CtxScalars {
 // the hash's two words are read back with one 8-byte copy
 static_assert(offsetof(CtxScalars, lh_overflow) ==
                   offsetof(CtxScalars, lh_counter) + 4, "");
+// ... and so are k_weld_plan's two
+static_assert(offsetof(CtxScalars, weld_table_labels) ==
+                  offsetof(CtxScalars, weld_nlist) + 4, "");
 
 struct SimpPlane;  // simplify.hip
 struct CmMisc;     // chunk_mesh.hip
@@ -98,19 +103,23 @@ struct DeviceBuffers {
   LabelVolume labels, holes;  // holes: fill_holes' resident hole volume
   DevBuf scan_tmp, sort_tmp;
   DevArr<uint64_t> lh_keys, label_values,
-      segcnt, segoff;  // per segment: (triangles << 32) | items
+      segcnt, segoff,  // per segment: (triangles << 32) | items
+      itscan;  // NI + 1: item -> (its first vertex << 32) | its first triangle
   // Between emit and weld the stream is per ITEM, one (cell, label) pair:
   // tri_label / tri_label_alt (the sort's keys), tri_keys, order /
-  // order_alt and itoff hold NI (+1) elements; lab_sorted, the slot
-  // triples and everything from the weld on are per triangle.
+  // order_alt and itscan hold NI (+1) elements; lab_sorted and everything
+  // from the weld on are per triangle.
   DevArr<uint32_t> lh_vals,
       tri_label, tri_label_alt, order, order_alt, tri_off,
-      itoff,        // NI + 1: item -> its first triangle of the stream
-      blk_item,     // first item of each 256-triangle block of the weld
-      lab_sorted,   // label id per triangle (k_weld_first)
-      keys_sorted,  // carved: tri_sort_view
-      vtx_scan,     // carved: weld_scan_view; simp_finalize's newid
-      wh_keys, faces, vbase;
+      lab_item,     // nlabels + 1: label -> its first item
+      blk_item,     // first item of each 256-triangle block of the stream
+      blk_list,     // the blocks the weld's global-table path runs over
+      lab_sorted,   // label id per triangle (the weld, when a simplify follows)
+      keys_sorted,  // the sort's alternate of tri_keys (2 NI words)
+      vtx_scan,     // simp_finalize's newid
+      wh_keys,      // the weld's global table (labels above WELD_LDS_CAP only)
+      faces, vbase;
+  DevArr<uint4> weld_quads;  // 3 slots + label per listed triangle
   DevArr<uint2> tri_keys;  // 8-B item records
   DevArr<float> verts;
   // simplifier
@@ -208,6 +217,7 @@ struct mg_ctx : DeviceBuffers {
   HostArr<float> h_verts;
   HostArr<uint32_t> h_faces;
   HostArr<uint8_t> h_blob;  // mg_mesh_chunk_encoded's blob, sized in bytes
+  HostArr<uint32_t> h_weld_err;  // CtxScalars::weld_err of the current call
   hipEvent_t ev[EV_COUNT_] = {};
 
   // release order: device buffers, pinned buffers, events, stream2, stream
@@ -217,6 +227,7 @@ struct mg_ctx : DeviceBuffers {
     h_verts.release();
     h_faces.release();
     h_blob.release();
+    h_weld_err.release();
     for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     if (stream2) (void)hipStreamDestroy(stream2);
     if (stream) (void)hipStreamDestroy(stream);
@@ -307,7 +318,7 @@ static int rocprim_two_call(mg_ctx *c, DevBuf &tmp, const char *err_size,
 // Exclusive plus-scan of n u32 values from `in` into `out` on stream s,
 // temp storage in c->scan_tmp. In is a template parameter only so that
 // each call site keeps the iterator type it always instantiated rocPRIM
-// with (uint32_t *, or the weld's popcount transform iterator).
+// with.
 template <typename In>
 static int scan_u32(mg_ctx *c, In in, uint32_t *out, size_t n, hipStream_t s,
                     const char *err_size, const char *err_run, int rc) {
@@ -329,15 +340,15 @@ static int scan_u64(mg_ctx *c, const uint64_t *in, uint64_t *out, size_t n,
       });
 }
 
-// Inclusive plus-scan of n u32 values: out[i] = in[0] + ... + in[i].
+// Inclusive plus-scan of n u64 values: out[i] = in[0] + ... + in[i].
 template <typename In>
-static int scan_incl_u32(mg_ctx *c, In in, uint32_t *out, size_t n,
+static int scan_incl_u64(mg_ctx *c, In in, uint64_t *out, size_t n,
                          hipStream_t s, const char *err_size,
                          const char *err_run, int rc) {
   return rocprim_two_call(
       c, c->scan_tmp, err_size, err_run, rc, [&](void *tmp, size_t &bytes) {
         return rocprim::inclusive_scan(tmp, bytes, in, out, n,
-                                       rocprim::plus<uint32_t>(), s);
+                                       rocprim::plus<uint64_t>(), s);
       });
 }
 

@@ -1363,7 +1363,7 @@ static int simp_finalize(mg_ctx *c, const SimpCall &k, uint64_t *p_T,
   if (ensure(c, c->simp_verts_alt, 3 * V + 3)) return 45;
   if (ensure(c, c->simp_vbase_alt, L + 1)) return 45;
   uint32_t *ref = c->simp_ref.get();
-  // the weld's scan buffer, free now: NC >= V words (weld_scan_view)
+  // V words, sized by the caller (run_weld, mg_simplify_mesh)
   uint32_t *newid = c->vtx_scan.get();
   HIP_TRY(c, hipMemsetAsync(ref, 0, V * 4, s), 45);
   if (T > 0)

@@ -124,6 +124,17 @@ class MgStatsEncode(MgStatsFill):
     ]
 
 
+class MgStatsWeld(MgStatsEncode):
+    """... and the weld's path counters behind ms_encode: labels welded
+    through a per-label LDS table, labels above weld_lds_cap vertices
+    (global table), and that cap."""
+    _fields_ = [
+        ("weld_lds_labels", ctypes.c_uint64),
+        ("weld_table_labels", ctypes.c_uint64),
+        ("weld_lds_cap", ctypes.c_uint64),
+    ]
+
+
 class _MgEncodeParams(ctypes.Structure):
     _fields_ = [
         ("format", ctypes.c_uint32),
@@ -379,7 +390,7 @@ def load_library() -> ctypes.CDLL:
         lib.mg_label_counts_free.argtypes = [ctypes.POINTER(_MgLabelCounts)]
         lib.mg_get_stats.restype = ctypes.c_int
         lib.mg_get_stats.argtypes = [ctypes.c_void_p,
-                                     ctypes.POINTER(MgStatsEncode)]
+                                     ctypes.POINTER(MgStatsWeld)]
         lib.mg_last_error.restype = ctypes.c_char_p
         lib.mg_last_error.argtypes = [ctypes.c_void_p]
         lib.mg_device_count.restype = ctypes.c_int
@@ -1006,7 +1017,7 @@ class Engine:
         return EncodedLevel(tuple(tuple(p) for p in nodes), sizes, blob)
 
     def stats(self) -> dict:
-        s = MgStatsEncode()
+        s = MgStatsWeld()
         rc = self.lib.mg_get_stats(self.ctx, ctypes.byref(s))
         if rc != 0:
             raise RuntimeError("mg_get_stats failed")

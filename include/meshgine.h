@@ -185,6 +185,11 @@ typedef struct {
                            the simplifier (0 for every other call; also
                            inside ms_total). ms_d2h is then the download of
                            the blob and the per-label tables. */
+  uint64_t weld_lds_labels;   /* labels welded through a per-label LDS table */
+  uint64_t weld_table_labels; /* labels above weld_lds_cap vertices, welded
+                                 through the global direct-addressed table */
+  uint64_t weld_lds_cap;      /* vertex cap of the LDS weld's top band; the two
+                                 bands below end at a half and a quarter of it */
 } mg_stats;
 
 /* Fragment encoding on the device (mg_mesh_chunk_encoded). The numbers are

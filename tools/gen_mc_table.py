@@ -143,6 +143,21 @@ def edge_need(e):
     return sum(1 << b for b in range(3) if EDGE_DOFF[e][b] == 0)
 
 
+def item_first_bits(tris, interior):
+    """One item = all triangles of one (cell, mask). Bit 3t+v set iff corner
+    v of triangle t is the first occurrence of its weld slot in the label's
+    stream: the edge's first use within the cell (tri_first_bits) in the
+    lowest cell holding the edge (edge_need against `interior`, bit b set
+    iff the cell's coordinate on axis b is above 0)."""
+    first = tri_first_bits(tris)
+    bits = 0
+    for t, tri in enumerate(tris):
+        for v, e in enumerate(tri):
+            if (first[t] >> v) & 1 and (edge_need(e) & interior) == 0:
+                bits |= 1 << (3 * t + v)
+    return bits
+
+
 def check_orientation():
     """Every single-corner mask must produce one triangle whose normal
     points AWAY from the labeled corner (outward)."""
@@ -230,6 +245,17 @@ def main():
         f.write("// below in b, if any, holds the edge too and is emitted first)\n")
         f.write("MC_TABLE_QUAL unsigned char MC_EDGE_NEED[12] = {\n")
         f.write("  " + ", ".join(str(edge_need(e)) for e in range(12)) + ",\n")
+        f.write("};\n\n")
+        f.write("// per (mask, interior): bit 3t+v set iff corner v of triangle t\n")
+        f.write("// is the first occurrence of its weld slot in its label's\n")
+        f.write("// stream, i.e. MC_TRI_FIRST[mask][t] bit v is set and\n")
+        f.write("// MC_EDGE_NEED[edge] & interior == 0; interior bit b = the\n")
+        f.write("// cell's coordinate on axis b is above 0. popcount = the\n")
+        f.write("// item's vertex count, popcount below a bit = the corner's rank\n")
+        f.write("MC_TABLE_QUAL unsigned short MC_ITEM_FIRST[256][8] = {\n")
+        for m in range(256):
+            f.write("  {" + ", ".join(f"0x{item_first_bits(table[m], i):04x}"
+                                      for i in range(8)) + "},\n")
         f.write("};\n\n")
         f.write("// corner ids (a,b) of each edge, a < b (a = lower voxel)\n")
         f.write("MC_TABLE_QUAL unsigned char MC_EDGE_CORNERS[12][2] = {\n")
